@@ -8,11 +8,18 @@ Nothing is skipped or cached inside the timed region; weights are seeded-synthet
 offline), activations fp16 with fp32 MFMA accumulation.
 
   python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W --full                 # + every other leg listed below
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR     # + what the last timed step computed, as DIR/*.npy
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
   python bench.py --config c4          # BASELINE configs[3]: DeOldify + DDColor merge (combine_method=2) at 1080p
 
 `value` is the fast mode (precision="fast", asked for explicitly; the package default is "precise" = the line's `contract` object).  It is the whole-job rate over the EXACTLY K timed steps (sum over all ranks; `value_per_gpu` = value / n_gpus); one step = 64 frames per GPU
-(--batch).  Beside it the line carries, measured in the same process after the timed region (rank 0, N = 1):
+(--batch); `ms_per_step` is the wall time of one timed step.  A plain run (no --full) does only that: set-up, W warm-up steps, the K timed steps, the
+optional output dump and the JSON line (with the `roofline` of the tail conv, whose launches are timed inside those same steps).
+--dump-outputs DIR writes, after the timed steps, the uint8 frames the last timed step handed back as float32 .npy files (every config: frames.npy = the
+step's first and last frames whole, pixels.npy = a seeded sample of 2^21 values over all of its frames; 58 MB at 1080p).  Inputs and weights are seeded:
+the same arguments give the same inputs in every run, so two builds can be compared output for output.
+With --full (rank 0, N = 1) the line also carries, measured in the same process after the timed region:
   precise        the same step with ModelImageRender(precision="precise") (fp32-class arithmetic; measured against the oracle: mean ~1e-3, p99 0.000,
                  >= 99.97 % of the pixels below CIEDE2000 1.0, residual maximum 2.5 - 3.6 = single truncation flips of uint8(x * 255), which two fp32
                  evaluations of the reference differ by as well), its own roofline and its parity against the same oracle frames.  Every parity object
@@ -27,9 +34,10 @@ offline), activations fp16 with fp32 MFMA accumulation.
                  render built without any precision switch (the package default)
   cpu_baseline / parity   the CPU oracle on one frame of the same clip, and the GPU frame against it
 
-Wall time of the default run (`python bench.py`, one MI355X box, round 5): about 4 minutes -- the five child legs (c3, c3 precise, c4, c4 precise, c5) 85 s, the
+Wall time of the --full run (`python bench.py --full`, one MI355X box, round 5): about 4 minutes -- the five child legs (c3, c3 precise, c4, c4 precise, c5) 85 s, the
 headline's warm-up + timed steps 10 s, the sustained / PCIe / per-frame-call legs 55 s, the precise leg 15 s, the CPU oracle on 8 frames 45 s.  --no-other-configs,
---no-extras, --no-precise and --no-cpu-baseline each drop their part; the JSON line says which legs ran.
+--no-extras, --no-precise and --no-cpu-baseline each drop their part of a --full run; the JSON line says which legs ran.  The same holds for --config c3 / c4 / c5:
+their CPU oracle + parity and their extra legs run with --full only.
 
 Multi-GPU: frames are independent — every rank colours its own shard on its own GPU with a
 full weight replica, no data-path collective; RCCL is used only for the barrier / max-over-ranks timing.
@@ -199,6 +207,23 @@ def off(p, nbytes):
     return ctypes.c_void_p(p.value + nbytes)
 
 
+DUMP_SAMPLES, DUMP_SEED = 1 << 21, 0
+
+
+def dump_outputs(dirname, frames):
+    """--dump-outputs: `frames` = the uint8 [N, H, W, 3] frames the last timed step handed back -> DIR/frames.npy (its first and last frames whole)
+    and DIR/pixels.npy (DUMP_SAMPLES values at flat positions drawn once from default_rng(DUMP_SEED): the same positions in every run of one
+    shape), both float32: 58 MB for a 1080p step."""
+    frames = np.asarray(frames)
+    os.makedirs(dirname, exist_ok=True)
+    whole = sorted({0, len(frames) - 1})
+    np.save(os.path.join(dirname, "frames.npy"), frames[whole].astype(np.float32))
+    flat = frames.reshape(-1)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.size, min(DUMP_SAMPLES, flat.size)))
+    np.save(os.path.join(dirname, "pixels.npy"), flat[idx].astype(np.float32))
+    _progress(f"outputs of the last timed step ({frames.shape}) written to {dirname}")
+
+
 _CPU_THREADS = {}
 
 
@@ -252,7 +277,14 @@ def main():
     ap.add_argument("--min-seconds", type=float, default=0.0,
                     help="c3 / c4 / c5: raise --steps (BEFORE the timed region, from one untimed probe step) so that the timed region lasts at least this long")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads for the CPU-oracle baseline leg (0 = all host cores: os.cpu_count())")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (other configs, precise mode, sustained / PCIe / per-frame calls, CPU oracle + parity); "
+                         "a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/*.npy (float32, a fixed seeded sample, < 64 MB)")
     args = ap.parse_args()
+    if not args.full:                   # a plain run: set-up, warm-up, the timed steps, the dump and the JSON line
+        args.no_cpu_baseline = args.no_extras = args.no_other_configs = args.no_precise = True
     if args.batch is None:              # 64 frames per step fill the small encoder / decoder layers better than 32 (+2 %, same-box A/B; 105 GB of activations)
         # c3 (DDColor): 64 frames = 65 536 tokens at the 768-channel stage -> 768 tiles of 256 x 256 for pwconv2 = exactly 3 per CU; at 32 frames
         # 384 tiles = 1.5 per CU and the GEMM runs at 75 % (profiles/r4_ddcolor_batch_sweep.txt: 1.09 -> 1.01 ms per frame of GPU ops)
@@ -297,15 +329,22 @@ def main():
     from vsdeoldify_amd.clip import ClipColorizer, synthetic_gray_frame
     from vsdeoldify_amd.synth import synth_state_dict
 
-    sds = {"video": synth_state_dict("wide", 1), "stable": synth_state_dict("wide", 2)}
+    # the seeded weights and frames are synthesised on a few host threads (each array has its own seed: the same bytes as one after the other), the
+    # frames while the weights are packed and uploaded
+    from concurrent.futures import ThreadPoolExecutor
+    n_clip = max(args.clip_frames, args.batch)
+    n_clip = (n_clip + args.batch - 1) // args.batch * args.batch
+    pool = ThreadPoolExecutor(max(1, min(8, os.cpu_count() or 1)))
+    weight_jobs = [pool.submit(synth_state_dict, "wide", s) for s in (1, 2)]
+    frame_jobs = [pool.submit(synthetic_gray_frame, rank * n_clip + i, WIDTH, HEIGHT) for i in range(n_clip)]
+    sds = {"video": weight_jobs[0].result(), "stable": weight_jobs[1].result()}
     # the headline is the opt-in speed mode, asked for explicitly; the package default is "precise" (vsdeoldify_amd/precision.py) = the `contract` leg
     cc = ClipColorizer("stable", RENDER_FACTOR, 0.5, device_index=local_rank, state_dicts=sds, max_batch=args.batch, precision="fast")
     ctx = cc.ctx
 
     # ---- synthetic clip, resident in HBM before the timed region --------------------------------
-    n_clip = max(args.clip_frames, args.batch)
-    n_clip = (n_clip + args.batch - 1) // args.batch * args.batch
-    frames = np.stack([synthetic_gray_frame(rank * n_clip + i, WIDTH, HEIGHT) for i in range(n_clip)])
+    frames = np.stack([j.result() for j in frame_jobs])
+    pool.shutdown()
     fbytes = WIDTH * HEIGHT * 3
     d_src, d_dst = ctx.dev_alloc(frames.nbytes), ctx.dev_alloc(frames.nbytes)
     ctx.dev_upload(d_src, frames)
@@ -336,6 +375,10 @@ def main():
     nat.check(ctx.lib.havc_tag_timing_read(ctx.h, ctypes.byref(avg_ms), ctypes.byref(launches)), ctx.h)
     nat.check(ctx.lib.havc_tag_timing_enable(ctx.h, TAG_TAIL_RES, 0), ctx.h)
     st = ctx.stats()
+    if args.dump_outputs and rank == 0:
+        last = np.empty((args.batch, HEIGHT, WIDTH, 3), np.uint8)
+        ctx.dev_download(last, off(d_dst, ((args.warmup + args.steps - 1) % n_batches) * args.batch * fbytes))
+        dump_outputs(args.dump_outputs, last)
 
     multi = None
     if dist is not None:
@@ -469,8 +512,8 @@ def other_configs_leg(args):
 
     def child(cfg, extra, steps, warm):
         _progress(f"child leg {cfg} {' '.join(extra)}")
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", steps, "--warmup", warm, "--no-extras", "--cpu-threads", str(args.cpu_threads),
-               "--min-seconds", str(CHILD_MIN_SECONDS)] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", steps, "--warmup", warm, "--full", "--no-extras",
+               "--cpu-threads", str(args.cpu_threads), "--min-seconds", str(CHILD_MIN_SECONDS)] + extra
         if args.no_cpu_baseline:
             cmd.append("--no-cpu-baseline")
         t0 = time.time()
@@ -707,6 +750,8 @@ def bench_c4(args, rank, local_rank, world, dist, ddcolor_only=False):
     nat.check(ctx.lib.havc_tag_timing_read(ctx.h, ctypes.byref(avg_ms), ctypes.byref(launches)), ctx.h)
     nat.check(ctx.lib.havc_tag_timing_enable(ctx.h, tag, 0), ctx.h)
     st = ctx.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, keep[0].numpy())
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local_rank}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -879,6 +924,8 @@ def bench_c5(args, rank, local_rank, world, dist):
     tctx.synchronize()
     nat.check(tctx.lib.havc_tag_timing_read(tctx.h, ctypes.byref(avg_ms), ctypes.byref(launches)), tctx.h)
     nat.check(tctx.lib.havc_tag_timing_enable(tctx.h, int(op["tag"]), 0), tctx.h)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, np.stack([o.numpy() for o in keep[0]]))
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local_rank}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
