@@ -75,10 +75,9 @@ def splitk_for(rows, Npad, Kc):
 class _Builder(PlanBuilder):
     """PlanBuilder that knows the batch count of the slice being emitted and adds the split-K count to its convs"""
     slice_batch = 1
-    auto_split = True
 
     def conv(self, name, pc, x, y, stride=1, pad=0, flags=0, **kw):
-        if self.auto_split and not (flags & (nat.F_W_FROM_BUF | nat.F_PS_BLUR | nat.F_FUSE_PROJ | nat.F_OUT_RGB8)):
+        if not (flags & (nat.F_W_FROM_BUF | nat.F_PS_BLUR | nat.F_FUSE_PROJ | nat.F_OUT_RGB8)):
             Ho, Wo = _conv_out(x.H, pc.kh, stride, pad), _conv_out(x.W, pc.kw, stride, pad)
             flags |= nat.F_SPLITK(splitk_for(Ho * Wo * self.slice_batch, pc.Npad, pc.Kc))
         return super().conv(name, pc, x, y, stride=stride, pad=pad, flags=flags, **kw)
@@ -309,7 +308,6 @@ class ColorMNetPlan:
         the key encoder several at a time (ColorMNetNetwork.prefetch_keys); the split-K counts of that slice are chosen for key_batch frames."""
         assert H % 112 == 0 and W % 112 == 0, "frames are padded to multiples of 112 (inference_core.py:49)"
         sd, b = self.sd, _Builder()
-        b.auto_split = os.environ.get("HAVC_CMN_SPLITK", "1") != "0"       # A/B switch (profiling)
         consts, sl, io = [], {}, {}
         CK, CV, HD = self.key_dim, self.value_dim, self.hidden_dim
         h16, w16, h8, w8, h4, w4 = H // 16, W // 16, H // 8, W // 8, H // 4, W // 4
@@ -603,19 +601,6 @@ class ColorMNetNetwork:
         """the network object the look-ahead pass runs on: another context (its own HIP stream and activation arena) of the same GPU, same packed
         weights.  The pass for the NEXT frames then overlaps the frame-by-frame memory step, whose small launches leave most CUs idle."""
         if self._helper is None:
-            from .render import get_context
-            hctx = get_context(self.ctx.device_id, ("lookahead", self.worker))
-            if os.environ.get("HAVC_CMN_LOOKAHEAD_PRIORITY", "0") == "low" and not getattr(hctx, "_low_priority", False):
-                # A/B switch, OFF: the look-ahead streams at the lowest stream priority.  The dispatcher then serves the memory step's queue first
-                # whenever both have a block ready -- and the batched pass, which the NEXT window cannot start without, starves: c5 1 031 -> 612
-                # frames/s (tools/sessions/r5_run14.sh).  (Before any stream handle of hctx is handed out.)
-                nat.check(hctx.lib.havc_ctx_set_stream_priority(hctx.h, -1), hctx.h)
-                hctx._low_priority = True
-            cus = int(os.environ.get("HAVC_CMN_LOOKAHEAD_CUS", "0"))
-            if cus > 0 and not getattr(hctx, "_cu_masked", False):
-                # the batched pass on `cus` of the 256 CUs: the rest stay free for the memory step's small dependent launches
-                nat.check(hctx.lib.havc_ctx_set_stream_cus(hctx.h, cus), hctx.h)
-                hctx._cu_masked = True
             self._helper = ColorMNetNetwork(None, device_index=self.ctx.device_id, autotune=self.autotune, worker=("lookahead", self.worker), share=self)
         return self._helper
 

@@ -10,7 +10,6 @@
 // v_mfma_f32_16x16x32_f16 so that every lane owns ONE query column: the online-softmax row max / sum are
 // in-lane reductions plus two wavefront shuffles (xor 16, xor 32).
 #include "kernels.h"
-#include <cstdlib>
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
@@ -328,8 +327,7 @@ int launch_attention(const half_t* qk, int qk_pitch, int f_coff, int g_coff, int
                      int npitch, const half_t* x, int x_cpitch, int x_coff, half_t* out, int o_cpitch, int o_coff,
                      int B, int N, float gamma, hipStream_t s) {
     if (dv % 128 != 0 || npitch % 64 != 0 || npitch < N) return (int)hipErrorInvalidValue;
-    static const bool v1 = getenv("HAVC_ATTENTION_V1") != nullptr;            // A/B switch (profiling)
-    if (dv % 256 == 0 && !v1) {
+    if (dv % 256 == 0) {
         dim3 grid2((N + 127) / 128, dv / 256, B);
         if (d == 64)
             hipLaunchKernelGGL(self_attention_kernel2<64>, grid2, dim3(256), 0, s, qk, qk_pitch, f_coff, g_coff, vT, dv, npitch, x, x_cpitch, x_coff,

@@ -2,7 +2,6 @@
 // Integer arithmetic follows OpenCV's 8-bit BT.601 "YUV" fixed point (yuv_shift = 14) and Pillow's
 // ImagingBlend exactly (bit-exact targets; see oracle/cvcolor.py, oracle/imaging.py).
 #include "kernels.h"
-#include <cstdlib>
 
 static inline int grid_for(int64_t work) {
     int64_t b = (work + 255) / 256;
@@ -384,11 +383,10 @@ int launch_resize_passes(const uint8_t* src, int sw, int sh, uint8_t* dst, int d
                          const int* h_start, const float* h_w, int h_taps, const int* v_start, const float* v_w,
                          int v_taps, const uint8_t* orig, hipStream_t s) {
     const int64_t rows = (int64_t)n_frames * sh;
-    static const bool old_h = getenv("HAVC_RESIZE_V1") != nullptr;             // A/B switch (profiling): the one-block-per-row horizontal pass
     // source span of a 256-column tile: 256 outputs step (sw / dw) source pixels each, plus the taps
     const size_t span_px = (size_t)((255.0 * sw) / dw) + h_taps + 4;
     const size_t lds_t = (span_px * 3 + 8 + 15) & ~(size_t)15;
-    if (!old_h && h_taps <= 48 && lds_t <= 4096) {                           // (spans up to 4 KiB: four prefetched dwords per thread)
+    if (h_taps <= 48 && lds_t <= 4096) {                // (spans up to 4 KiB: four prefetched dwords per thread)
         const int xt = (dw + 255) / 256;
         // 16 rows per block amortise the per-thread tap loads; a single frame (ColorMNet: one squash per call) does not fill the chip that way and
         // keeps the one-block-per-row pass (measured: c5 -0.7 % with one row per block here)
@@ -416,7 +414,7 @@ int launch_resize_passes(const uint8_t* src, int sw, int sh, uint8_t* dst, int d
     }
 vertical:
     const int groups = (dh + VR - 1) / VR;
-    const bool quad = !old_h && (dw & 3) == 0 && ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(orig)) & 3) == 0 &&
+    const bool quad = (dw & 3) == 0 && ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(orig)) & 3) == 0 &&
                       (reinterpret_cast<uintptr_t>(tmp) & 15) == 0;
     if (quad)
         hipLaunchKernelGGL(resize_v4_kernel, dim3(grid_for((int64_t)n_frames * groups * (dw >> 2))), dim3(256), 0, s, tmp, dst, orig,

@@ -3,7 +3,6 @@
 #include "kernels.h"
 #include <algorithm>
 #include <atomic>
-#include <cstdlib>
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
@@ -485,13 +484,9 @@ static void dwln_optin() {                                  // > 64 KiB of dynam
 }
 // every instantiation launch_dwconv7_ln may pick: opted in eagerly from havc_create (see preload_elementwise)
 void preload_ddcolor() {
-    dwln_optin<16, true, 768, false>();
-    dwln_optin<48, true, 512, true>(); dwln_optin<48, true, 768, false>();
-    dwln_optin<96, true, 512, true>(); dwln_optin<96, true, 768, false>();
-    dwln_optin<192, true, 512, true>(); dwln_optin<192, true, 768, false>();
-    dwln_optin<384, false, 768, false>(); dwln_optin<384, false, 512, true>();
+    dwln_optin<16, true, 768, false>(); dwln_optin<48, true, 768, false>(); dwln_optin<96, true, 768, false>(); dwln_optin<192, true, 768, false>();
+    dwln_optin<384, false, 512, true>();
     dwln_optin<48, true, 512, false, true>(); dwln_optin<96, true, 512, false, true>(); dwln_optin<192, true, 512, false, true>();      // precise
-    dwln_optin<48, true, 512, false>(); dwln_optin<96, true, 512, false>(); dwln_optin<192, true, 512, false>();                        // HAVC_DWLN_VARIANT=3
     (void)hipGetLastError();
 }
 
@@ -512,15 +507,13 @@ int launch_dwconv7_ln(const half_t* x, const half_t* w, const float* bias, const
                       int H, int W, int C, int x_cpitch, int x_coff, int y_cpitch, int y_coff, int w_pitch, hipStream_t s) {
     const size_t xb = ((size_t)B * H * W * x_cpitch + x_coff) * 2;
     if (!dwconv7_ln_supported(C) || xb >= DWLN_OOB) return (int)hipErrorInvalidValue;
-    static const int variant = [] { const char* e = getenv("HAVC_DWLN_VARIANT"); return e ? atoi(e) : 0; }();      // A/B switch (profiling)
 #define DWLN_ARGS x, w, bias, gamma, beta, eps, y, B, H, W, (unsigned)xb, x_cpitch, x_coff, y_cpitch, y_coff, w_pitch, s
     switch (C) {
         case 64: return launch_dwln<16, true, 768, false>(DWLN_ARGS);
-        // variant 3 (round 6 A/B): 512 threads, one output row per step -- the geometry of the precise form (no spills, 2 waves per SIMD)
-        case 192: return variant == 3 ? launch_dwln<48, true, 512, false>(DWLN_ARGS) : variant == 1 ? launch_dwln<48, true, 512, true>(DWLN_ARGS) : launch_dwln<48, true, 768, false>(DWLN_ARGS);
-        case 384: return variant == 3 ? launch_dwln<96, true, 512, false>(DWLN_ARGS) : variant == 1 ? launch_dwln<96, true, 512, true>(DWLN_ARGS) : launch_dwln<96, true, 768, false>(DWLN_ARGS);
-        case 768: return variant == 3 ? launch_dwln<192, true, 512, false>(DWLN_ARGS) : variant == 1 ? launch_dwln<192, true, 512, true>(DWLN_ARGS) : launch_dwln<192, true, 768, false>(DWLN_ARGS);
-        case 1536: return variant == 2 ? launch_dwln<384, false, 768, false>(DWLN_ARGS) : launch_dwln<384, false, 512, true>(DWLN_ARGS);
+        case 192: return launch_dwln<48, true, 768, false>(DWLN_ARGS);
+        case 384: return launch_dwln<96, true, 768, false>(DWLN_ARGS);
+        case 768: return launch_dwln<192, true, 768, false>(DWLN_ARGS);
+        case 1536: return launch_dwln<384, false, 512, true>(DWLN_ARGS);
     }
 #undef DWLN_ARGS
     return (int)hipErrorInvalidValue;
@@ -704,85 +697,15 @@ int launch_mha32(const half_t* q, int q_cpitch, int q_coff, int q_tok, const hal
     return (int)hipGetLastError();
 }
 
-// ---- the same attention, split over the keys (flash-decoding form): what DDColor's cross-attention needs (100 queries against up
-// to 16 384 keys: one wave per query re-reads every K / V row 100 times).  Block (split c, head h, frame b), one thread per query:
-// the block stages KC keys of K and V in LDS once (every thread then reads the SAME row: LDS broadcast), each thread runs its
-// query over them with an online softmax (rescaled once per 8 keys) and writes {m, l, acc[32]}; mha32_merge_kernel folds the splits.
-constexpr int MHA_KC = 256;
-__global__ void __launch_bounds__(128) mha32_split_kernel(const half_t* __restrict__ q, int q_cpitch, int q_coff, int q_tok,
-                                                          const half_t* __restrict__ kv, int kv_cpitch, int k_coff, int v_coff, int kv_tok,
-                                                          float* __restrict__ part, int heads, int Lq, int Lk, float scale) {
-    __shared__ __attribute__((aligned(16))) half_t Ks[MHA_KC][32];
-    __shared__ __attribute__((aligned(16))) half_t Vs[MHA_KC][32];
-    const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z, nsplit = gridDim.x;
-    const int k0 = c * MHA_KC, nk = min(MHA_KC, Lk - k0);
-    const half_t* kb = kv + ((int64_t)b * kv_tok + k0) * kv_cpitch + h * 32;
-    for (int i = threadIdx.x; i < nk * 8; i += blockDim.x) {                // 8 16-byte chunks per key: 4 of K, 4 of V
-        const int key = i >> 3, ch = i & 7;
-        const half8 t = *reinterpret_cast<const half8*>(kb + (int64_t)key * kv_cpitch + (ch < 4 ? k_coff + ch * 8 : v_coff + (ch - 4) * 8));
-        *reinterpret_cast<half8*>(ch < 4 ? &Ks[key][ch * 8] : &Vs[key][(ch - 4) * 8]) = t;
-    }
-    __syncthreads();
-    for (int iq = threadIdx.x; iq < Lq; iq += blockDim.x) {
-        float qv[32], acc[32];
-        const half_t* qp = q + ((int64_t)b * q_tok + iq) * q_cpitch + q_coff + h * 32;
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) {
-            const half8 t = *reinterpret_cast<const half8*>(qp + cc * 8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { qv[cc * 8 + e] = (float)t[e] * scale; acc[cc * 8 + e] = 0.f; }
-        }
-        float m = -INFINITY, l = 0.f;
-        for (int j0 = 0; j0 < nk; j0 += 8) {
-            float sc[8];
-            float gmax = m;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float d = -INFINITY;
-                if (j0 + j < nk) {
-                    d = 0.f;
-#pragma unroll
-                    for (int cc = 0; cc < 4; ++cc) {
-                        const half8 t = *reinterpret_cast<const half8*>(&Ks[j0 + j][cc * 8]);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) d += qv[cc * 8 + e] * (float)t[e];
-                    }
-                }
-                sc[j] = d;
-                gmax = fmaxf(gmax, d);
-            }
-            const float corr = __expf(m - gmax);                              // m = -inf on the first group: corr = 0, acc is 0 anyway
-            l *= corr;
-#pragma unroll
-            for (int e = 0; e < 32; ++e) acc[e] *= corr;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                if (j0 + j < nk) {
-                    const float pj = __expf(sc[j] - gmax);
-                    l += pj;
-#pragma unroll
-                    for (int cc = 0; cc < 4; ++cc) {
-                        const half8 t = *reinterpret_cast<const half8*>(&Vs[j0 + j][cc * 8]);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) acc[cc * 8 + e] += pj * (float)t[e];
-                    }
-                }
-            }
-            m = gmax;
-        }
-        float* o = part + ((((int64_t)b * heads + h) * nsplit + c) * Lq + iq) * 34;
-        o[0] = m; o[1] = l;
-#pragma unroll
-        for (int e = 0; e < 32; ++e) o[2 + e] = acc[e];
-    }
-}
-// ---- the key-split attention on MFMA (round 2).  Same splitting and the same {m, l, acc[32]} partial states as mha32_split_kernel
-// (mha32_merge_kernel folds them); what changes is who does the arithmetic: a block (split of 256 keys, head, frame) = 4 waves, a
-// wave owns up to two 16-query fragments.  Head dim 32 is exactly the K of v_mfma_f32_16x16x32_f16:
+// ---- the same attention, split over the keys (flash-decoding form) on MFMA: what DDColor's cross-attention needs (100 queries against
+// up to 16 384 keys: one wave per query re-reads every K / V row 100 times).  A block (split of 256 keys, head, frame) = 4 waves, a
+// wave owns up to two 16-query fragments; it runs its queries over the keys with an online softmax and writes {m, l, acc[32]} per
+// query; mha32_merge_kernel folds the splits.  Head dim 32 is exactly the K of v_mfma_f32_16x16x32_f16:
 //   S^T[key][query] = K[key][:] . Q[query][:]      A = K rows straight from global (16 B per lane: row = key, chunk = lane >> 4)
 //   O^T[dv][query]  = V^T[dv][key] . P^T[key][query] A = V^T from an LDS image transposed while staging, B = P from registers
 // S fragment f covers keys 32 (f >> 1) + (i >> 2) 8 + (f & 1) 4 + (i & 3) (i = MFMA row), so that a lane's eight P values of two
 // neighbouring fragments are keys lg * 8 .. + 7 of a 32-key step in natural order: the second MFMA's B operand needs no shuffle.
+constexpr int MHA_KC = 256;
 typedef float float4v_dd __attribute__((ext_vector_type(4)));
 constexpr int MHA_VP = MHA_KC + 8;                 // V^T row pitch (halfs): 528 B rows spread the 16 rows of a fragment read over the banks
 // Round 4: a block walks `nch` consecutive 256-key chunks of its (head, frame) with a running (max, sum, acc) per query fragment before it writes
@@ -910,22 +833,13 @@ int mha32_nsplit(int Lk) { return (Lk + MHA_KC - 1) / MHA_KC; }
 int launch_mha32_split(const half_t* q, int q_cpitch, int q_coff, int q_tok, const half_t* kv, int kv_cpitch, int k_coff, int v_coff, int kv_tok,
                        half_t* o, int o_cpitch, int o_coff, int o_tok, float* part, int B, int heads, int Lq, int Lk, float scale, hipStream_t s) {
     const int nchunks = mha32_nsplit(Lk);                                     // 256-key chunks; the partial-state buffer is sized for one split per chunk
-    static const bool v1 = getenv("HAVC_MHA_V1") != nullptr;                  // A/B switch (profiling): the one-thread-per-query kernel
-    static const int nch_env = [] { const char* e = getenv("HAVC_MHA_NCH"); return e ? atoi(e) : 0; }();       // A/B: chunks per block (0 = automatic)
     // chunks per block: as many (<= 4) as keep >= 1 024 blocks in flight (one frame of the coarse level stays at one chunk per block)
-    int nch = 1;
-    if (!v1) {
-        const int64_t blocks1 = (int64_t)nchunks * heads * B;
-        nch = nch_env > 0 ? nch_env : (int)std::min<int64_t>(4, std::max<int64_t>(1, blocks1 / 1024));
-        nch = std::max(1, std::min(nch, nchunks));
-    }
+    const int64_t blocks1 = (int64_t)nchunks * heads * B;
+    int nch = (int)std::min<int64_t>(4, std::max<int64_t>(1, blocks1 / 1024));
+    nch = std::max(1, std::min(nch, nchunks));
     const int nsplit = (nchunks + nch - 1) / nch;
-    if (v1)
-        hipLaunchKernelGGL(mha32_split_kernel, dim3(nsplit, heads, B), dim3(128), 0, s, q, q_cpitch, q_coff, q_tok, kv, kv_cpitch, k_coff, v_coff, kv_tok,
-                           part, heads, Lq, Lk, scale);
-    else
-        hipLaunchKernelGGL(mha32_split_mfma_kernel, dim3(nsplit, heads, B), dim3(256), 0, s, q, q_cpitch, q_coff, q_tok, kv, kv_cpitch, k_coff, v_coff,
-                           kv_tok, part, heads, Lq, Lk, scale, nch);
+    hipLaunchKernelGGL(mha32_split_mfma_kernel, dim3(nsplit, heads, B), dim3(256), 0, s, q, q_cpitch, q_coff, q_tok, kv, kv_cpitch, k_coff, v_coff,
+                       kv_tok, part, heads, Lq, Lk, scale, nch);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(mha32_merge_kernel, dim3(grid_for_dd((int64_t)B * heads * Lq * 4)), dim3(256), 0, s, part, o, o_cpitch, o_coff, o_tok, B, heads,

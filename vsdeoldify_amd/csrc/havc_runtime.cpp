@@ -667,7 +667,7 @@ int run_op(havc_net* n, const havc_op& op, int batch) {
                 break;
             }
             if (op.flags & HAVC_F_PRECISE) {
-                // precise form: src = the last_shuf conv's pair tensor [Hi][Wi][16 x 256], aux0 = the folded projection (fp32 [2][256] per frame, FOLD_QUERIES)
+                // precise form without the fused conv (no plan of the package emits it; the op accepts it): src = the last_shuf conv's pair tensor [Hi][Wi][16 x 256], aux0 = the folded projection (fp32 [2][256] per frame, FOLD_QUERIES)
                 if (op.w_off < 0 || op.bias_off < 0 || op.src2 < 0 || op.aux0 < 0 || op.aux0 >= (int)n->bufs.size() || n->bufdesc[op.aux0].elem_bytes != 4 ||
                     (uint64_t)n->bufdesc[op.aux0].elems_per_frame < 512 || n->bufdesc[op.src].elem_bytes != 2 || op.Ci != 16 * 256)
                     return fail(c, HAVC_E_INVALID, "shuffle+blur(ab) op, precise: weights, image view, projection buffer (aux0), 4096-channel pair source");
@@ -2263,10 +2263,9 @@ int havc_memory_read_topk_usage(havc_ctx* c, const float* mk, const float* ms, c
     const size_t lst = (size_t)B * top_k * HW, cand = lst * (mem_topk_splits(N) > 1 ? mem_topk_splits(N) : 0);
     if ((rc = ensure_scratch(c, 8, (size_t)B * N * HW * 4)) || (rc = ensure_scratch(c, 9, (lst + cand) * 4)) ||
         (rc = ensure_scratch(c, 10, (lst + cand) * 4))) return rc;
-    // wave-per-query selection on a query-major similarity (HAVC_TOPK_WAVE=0: the two-level kernels; also beyond 16 384 memory elements)
-    static const bool wave_topk = [] { const char* e = getenv("HAVC_TOPK_WAVE"); return !e || atoi(e) != 0; }();
+    // wave-per-query selection on a query-major similarity; beyond 16 384 memory elements the two-level kernels
     int e;
-    if (wave_topk && mem_topk_select_supported(N)) {
+    if (mem_topk_select_supported(N)) {
         e = launch_mem_similarity_t(d_mk, d_ms, d_qk, d_qe, (float*)c->scratch[8], B, CK, N, HW, c->stream);
         if (!e) e = launch_mem_topk_select_readout((const float*)c->scratch[8], d_mv, (int*)c->scratch[9], (float*)c->scratch[10], (float*)d_out, B, CV, N, HW,
                                                    top_k, c->stream);
@@ -2470,9 +2469,8 @@ int havc_memory_read_banked(havc_ctx* c, const float* mk, const float* ms, const
     if ((rc = ensure_scratch(c, 14, (size_t)N * HW * 4)) || (rc = ensure_scratch(c, 15, (lst + cand) * 4)) || (rc = ensure_scratch(c, 16, (lst + cand) * 4))) return rc;
     const hipStream_t st = c->side ? c->stream2 : c->stream;       // a read-ahead (havc_cmn_side_begin) runs next to the previous frame's decoder
     stream_jitter(st);
-    static const bool wave_topk = [] { const char* e = getenv("HAVC_TOPK_WAVE"); return !e || atoi(e) != 0; }();
     int e;
-    if (wave_topk && mem_topk_select_supported(N)) {
+    if (mem_topk_select_supported(N)) {
         e = launch_mem_similarity_t(mk, ms, qk, qe, (float*)c->scratch[14], 1, CK, N, HW, st, pitch);
         if (!e) e = launch_mem_topk_select_readout((const float*)c->scratch[14], mv, (int*)c->scratch[15], (float*)c->scratch[16], out, 1, CV, N, HW, top_k, st, pitch);
     } else {

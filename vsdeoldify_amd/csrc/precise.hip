@@ -8,7 +8,6 @@
 // All kernels are HBM-bound except the attention, which is fp32 VALU (the N x N map of fastai's SelfAttention never leaves the CU).
 #include "conv_common.h"
 #include <atomic>
-#include <cstdlib>
 
 namespace {
 
@@ -669,8 +668,7 @@ int launch_attention_pm(const half_t* qk, int qk_cpitch, int f_coff, int g_coff,
     PAttnArgs a{};
     a.qk = qk; a.stats = stats; a.qk_cp = qk_cpitch; a.f_co = f_coff; a.g_co = g_coff; a.d = d; a.B = B; a.N = N; a.C = C; a.qk_fs = qk_fs;
     const int DP = d + 4, NJ = (N + PA_TJ - 1) / PA_TJ;
-    static const bool s_mfma = [] { const char* e = getenv("HAVC_PRECISE_ATTN_S_MFMA"); return e ? atoi(e) != 0 : true; }();      // A/B: 0 = S on the fp32 VALU
-    const bool smf = s_mfma && (d == 64 || d == 96) && (qk_cpitch & 15) == 0 && (f_coff & 7) == 0 && (g_coff & 7) == 0;
+    const bool smf = (d == 64 || d == 96) && (qk_cpitch & 15) == 0 && (f_coff & 7) == 0 && (g_coff & 7) == 0;
     if (smf) {
         if (d == 64) hipLaunchKernelGGL(pattn_stats_mfma_kernel<2>, dim3(NJ, B), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(pattn_stats_mfma_kernel<3>, dim3(NJ, B), dim3(256), 0, s, a);

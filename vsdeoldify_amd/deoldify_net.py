@@ -13,8 +13,7 @@ from .plan import (TAG_TAIL_RES, PlanBuilder, View, WeightPack, bn_scale_shift, 
                    pad_to, pitch_for, to_np)
 
 RESNET = {"wide": ("bottleneck", [3, 4, 23, 3]), "deep": ("basic", [3, 4, 6, 3])}
-import os
-FUSE_BLUR_MIN_H = int(os.environ.get("HAVC_FUSE_BLUR_MIN_H", "64"))      # smallest low-res side the fused shuffle + blur conv is used for
+FUSE_BLUR_MIN_H = 64           # smallest low-res side the fused shuffle + blur conv is used for
 Y_RANGE = (-3.0, 3.0)          # SigmoidRange(*y_range), deoldify/generators.py:33,111
 
 
@@ -56,11 +55,6 @@ class DeoldifyGenerator:
         same fusions as the fast plan (shuffle + blur since round 6, layers.11 + SigmoidRange + u8 since round 5) with fp32 epilogues."""
         assert arch in RESNET and precision in ("fast", "precise")
         self.precise = precision == "precise"
-        if self.precise:
-            # round 6: the fused shuffle + blur epilogue exists for pairs too (two passes of 32 channels through the 128 KiB LDS image,
-            # conv_pipe_epilogue.inc); HAVC_PRECISE_FUSE_BLUR=0 keeps the two-op chain (A/B runs; same bytes)
-            fuse_blur = fuse_blur and os.environ.get("HAVC_PRECISE_FUSE_BLUR", "1") != "0"
-            fuse_final = fuse_final and os.environ.get("HAVC_PRECISE_FUSE_FINAL", "1") != "0"      # round 5: layers.11 + SigmoidRange + u8 in the precise epilogue
         self.sd, self.arch, self.fuse_final, self.fuse_blur = to_np(state_dict), arch, fuse_final, fuse_blur
         self.pack, self._pc, self._vec = WeightPack(), {}, {}
         self._frozen = False
@@ -165,7 +159,7 @@ class DeoldifyGenerator:
         qk = b.tensor(x.H, x.W, 2 * d)
         b.conv(p + ".qk", pc_qk, x, qk)
         N = x.H * x.W
-        if self.precise and C % 256 == 0 and d % 8 == 0 and d <= 128 and os.environ.get("HAVC_PRECISE_ATTN_MFMA", "1") != "0":
+        if self.precise and C % 256 == 0 and d % 8 == 0 and d <= 128:
             # round 5: the value conv stores its map TRANSPOSED as two planes [2][C][npitch] (hi, lo) and the attention's P . H product runs on
             # MFMA with the three-term splitting (11.3 -> ~3 ms per 16 frames at 560 x 560); S = f . g and the softmax stay fp32 VALU
             npitch = pad_to(N, 64)
