@@ -401,6 +401,33 @@ int havc_image_tweak(havc_ctx* ctx, const uint8_t* img, uint8_t* out, int width,
  * HAVC_colorizer's default ddtweak_p[1] = "300:360|0.8,0.1"; sat / bright / hue are ignored. */
 int havc_image_chroma_tweak(havc_ctx* ctx, const uint8_t* img, uint8_t* out, int width, int height, double sat, double bright, int hue,
                             int has_adjust, const double* hue_ranges, int n_ranges, double adj_sat, int adj_hue, double adj_weight);
+/* HAVC_stabilizer's filter chain (vsdeoldify/__init__.py:2850-2860) in ONE launch: vs_dark_tweak -> vs_chroma_bright_tweak -> vs_colormap, whose
+ * per-frame bodies (vsslib/vsfilters.py:525-641) are "tweak the frame, then merge the tweaked frame with the frame under a luma mask".  A stage is one
+ * such body; up to three run back to back on every pixel in registers, with the arithmetic of the single entry points above (the same device functions):
+ * a chain gives the bytes of havc_image_tweak / havc_image_chroma_tweak + havc_image_luma_merge called one after the other. */
+typedef struct havc_stab_stage {
+    int kind;           /* 0: havc_image_tweak with contrast 1 (vs_sc_dark_tweak: Pillow HSV / ImageEnhance); 1: havc_image_chroma_tweak (cv2 HSV;
+                         * vs_sc_chroma_bright_tweak, _vs_sc_colormap) */
+    int merge_mode;     /* -1: the stage's result is the tweaked pixel (vs_colormap; w_image_luma_merge with dark_luma >= white_luma);
+                         * 0..3: havc_image_luma_merge(img_dark = tweaked, img_white = the stage's input, mode, tresh, grad) */
+    double tresh, grad; /* merge_mode 0: tresh; merge_mode 1: tresh and grad; otherwise ignored */
+    int hue_offset;     /* kind 0: Pillow hue units, as havc_image_tweak */
+    float brightness;   /* kind 0: ImageEnhance.Brightness factor (1 = step skipped) */
+    float color;        /* kind 0: ImageEnhance.Color factor (1 = step skipped) */
+    int identity;       /* kind 1: != 0 = the tweak returns its input (np_image_chroma_tweak's early return for sat 1, bright 0, hue 0, hue_adjust
+                         * "none", vsslib/restcolor.py:290-291 -- NOT the same bytes as an HSV round trip); the merge still runs */
+    double sat, bright; /* kind 1: as havc_image_chroma_tweak */
+    int hue;            /* kind 1: degrees */
+    int has_adjust;     /* kind 1: 0 / 1 = without / with the parsed "hue_adjust" stage (needs n_ranges >= 1); 2 is not a stabilizer filter: refused */
+    double adj_sat;     /* kind 1, has_adjust: saturation of the re-tweaked colour */
+    int adj_hue;        /* kind 1, has_adjust: its hue shift in degrees */
+    int n_ranges;       /* both kinds: hue ranges in use, 0..8 (kind 0: mask on the original's hue, 0 = none; kind 1: ranges of the adjust stage) */
+    double adj_weight;  /* kind 1, has_adjust: merge weight (sign and meaning as havc_image_chroma_tweak) */
+    double hue_ranges[16]; /* lo0, hi0, lo1, hi1, ... in degrees */
+} havc_stab_stage;
+/* img -> out through stages[0 .. n_stages - 1], n_stages 0..3 (0: out = img).  width x height pixels: a stack of frames is one tall image.  Host or
+ * device pointers like every filter here; out may be img.  A kind, merge_mode, has_adjust or n_ranges outside the values above: HAVC_E_INVALID, nothing runs. */
+int havc_stabilizer_chain(havc_ctx* ctx, const uint8_t* img, uint8_t* out, int width, int height, const havc_stab_stage* stages, int n_stages);
 /* the per-pixel half of luma_adjusted_levels (vsslib/imfilters.py:335-372): cv2 RGB->YUV, Y' = lut[Y], YUV->RGB.  The caller
  * derives the 256-entry table from havc_image_luma exactly like the reference (vsdeoldify_amd/imfilters.py). */
 int havc_luma_lut(havc_ctx* ctx, const uint8_t* img, const uint8_t* lut256, uint8_t* out, int width, int height);

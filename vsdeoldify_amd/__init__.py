@@ -19,7 +19,7 @@ def __getattr__(name):
     if name == "DDColorRender":
         from .ddcolor import DDColorRender
         return DDColorRender
-    if name in ("HAVC_colorizer", "HAVC_merge", "HAVC_ddeoldify", "ddeoldify", "HAVCFrameColorizer"):
+    if name in ("HAVC_colorizer", "HAVC_merge", "HAVC_ddeoldify", "ddeoldify", "HAVC_stabilizer", "HAVCFrameColorizer"):
         from . import havc
         return getattr(havc, name)
     if name == "DeviceImage":

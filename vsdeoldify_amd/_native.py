@@ -58,6 +58,15 @@ class Stats(C.Structure):
                 ("frames", C.c_int64), ("launches", C.c_int64), ("bytes_resident", C.c_int64)]
 
 
+class StabStage(C.Structure):
+    """`havc_stab_stage` (include/havc_mi355.h): one filter of the HAVC_stabilizer chain, tweak + luma-masked merge"""
+    _fields_ = [("kind", C.c_int), ("merge_mode", C.c_int), ("tresh", C.c_double), ("grad", C.c_double),
+                ("hue_offset", C.c_int), ("brightness", C.c_float), ("color", C.c_float), ("identity", C.c_int),
+                ("sat", C.c_double), ("bright", C.c_double), ("hue", C.c_int), ("has_adjust", C.c_int),
+                ("adj_sat", C.c_double), ("adj_hue", C.c_int), ("n_ranges", C.c_int), ("adj_weight", C.c_double),
+                ("hue_ranges", C.c_double * 16)]
+
+
 class NativeLibraryError(RuntimeError):
     pass
 
@@ -117,6 +126,7 @@ SYMBOLS = [
     ("havc_image_luma", _I, [_P, _P, _I, _I, C.POINTER(C.c_double)]),
     ("havc_image_tweak", _I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, C.POINTER(C.c_double), _I]),
     ("havc_image_chroma_tweak", _I, [_P, _P, _P, _I, _I, _D, _D, _I, _I, C.POINTER(C.c_double), _I, _D, _I, _D]),
+    ("havc_stabilizer_chain", _I, [_P, _P, _P, _I, _I, _P, _I]),
     ("havc_luma_lut", _I, [_P, _P, _P, _P, _I, _I]),
     ("havc_restore_color_gradient", _I, [_P, _P, _P, _P, _I, _I, _D, _I, _D, _D, _I, _I]),
     ("havc_colorize_clip", _I, [_P, _P, _P, _F, _P, _P, _I, _I, _I]),

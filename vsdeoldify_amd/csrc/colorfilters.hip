@@ -2,6 +2,7 @@
 // Integer arithmetic follows OpenCV's 8-bit BT.601 "YUV" fixed point (yuv_shift = 14) and Pillow's
 // ImagingBlend exactly (bit-exact targets; see oracle/cvcolor.py, oracle/imaging.py).
 #include "kernels.h"
+#include "pixel_ops.h"
 
 static inline int grid_for(int64_t work) {
     int64_t b = (work + 255) / 256;
@@ -432,36 +433,9 @@ vertical:
 __global__ void luma_merge_kernel(const uint8_t* __restrict__ dark, const uint8_t* __restrict__ white, int mode, double tresh,
                                   double grad, uint8_t* __restrict__ out, int64_t npix) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
-        const int r2 = white[i * 3], g2 = white[i * 3 + 1], b2 = white[i * 3 + 2];
-        double luma = ((double)r2 * 0.299 + (double)g2 * 0.587) + (double)b2 * 0.114;
-        luma = fmin(fmax(luma, 0.0), 255.0);
-        if (mode == 0) {
-            const bool wsel = luma > tresh;
-            out[i * 3] = wsel ? (uint8_t)r2 : dark[i * 3];
-            out[i * 3 + 1] = wsel ? (uint8_t)g2 : dark[i * 3 + 1];
-            out[i * 3 + 2] = wsel ? (uint8_t)b2 : dark[i * 3 + 2];
-            continue;
-        }
-        double wgt;
-        if (mode == 1) {
-            double lg = (luma - tresh) * grad;
-            float w32 = (float)(lg > 1.0 ? 1.0 : lg);          // array_max(.., 1.0).astype(float32)
-            w32 = w32 < 0.0f ? 0.0f : w32;                      // array_min(.., 0.0).astype(float32)
-            wgt = (double)w32;
-        } else if (mode == 2) {
-            wgt = luma / 255.0;                                 // w_np_rgb_to_gray(as_weight=True, dark_luma <= 0)
-        } else {
-            wgt = (double)(int)luma / 255.0;                    // image_luma_merge(luma=0): mask stored as uint8, then / 255
-        }
-        const double wb = 1.0 - wgt;
-        const int white_px[3] = {r2, g2, b2};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double p1 = (double)dark[i * 3 + c] * wb;
-            const double p2 = (double)white_px[c] * wgt;
-            const double v = fmin(fmax(p1 + p2, 0.0), 255.0);
-            out[i * 3 + c] = (uint8_t)(int)v;
-        }
+        int r, g, b;
+        luma_merge_pixel(mode, tresh, grad, dark[i * 3], dark[i * 3 + 1], dark[i * 3 + 2], white[i * 3], white[i * 3 + 1], white[i * 3 + 2], r, g, b);
+        out[i * 3] = (uint8_t)r; out[i * 3 + 1] = (uint8_t)g; out[i * 3 + 2] = (uint8_t)b;
     }
 }
 

@@ -987,7 +987,7 @@ static void preload_device_locked(int dev) {
     static uint64_t done = 0;                              // guarded by g_setup_mu
     if (done & (1ull << (dev & 63))) return;
     preload_conv_pipe(); preload_conv_igemm(); preload_elementwise(); preload_zhang(); preload_attention(); preload_colorfilters();
-    preload_tweaks(); preload_ddcolor(); preload_colormnet(); preload_colormnet_net(); preload_precise(); preload_precise2();
+    preload_tweaks(); preload_stabilizer(); preload_ddcolor(); preload_colormnet(); preload_colormnet_net(); preload_precise(); preload_precise2();
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(scratch_warm_kernel));
     (void)hipGetLastError();
@@ -1929,10 +1929,9 @@ int havc_image_tweak(havc_ctx* c, const uint8_t* img, uint8_t* out, int width, i
     return stage_out(c, out, dout, nb, host);
 }
 
-int havc_image_chroma_tweak(havc_ctx* c, const uint8_t* img, uint8_t* out, int width, int height, double sat, double bright, int hue,
-                            int has_adjust, const double* hue_ranges, int n_ranges, double adj_sat, int adj_hue, double adj_weight) {
-    if (!c || !img || !out || width <= 0 || height <= 0 || n_ranges < 0 || n_ranges > HAVC_MAX_HUE_RANGES || (has_adjust && (!hue_ranges || n_ranges < 1)))
-        return fail(c, HAVC_E_INVALID, "image_chroma_tweak: bad args (1..8 hue ranges with an adjust stage)");
+// the argument normalisation of np_image_chroma_tweak (restcolor.py:288-350): clamps, half-degree hue steps, which sub-steps run
+static ChromaTweakArgs chroma_tweak_args(double sat, double bright, int hue, int has_adjust, const double* hue_ranges, int n_ranges, double adj_sat,
+                                         int adj_hue, double adj_weight) {
     auto clampd = [](double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); };
     ChromaTweakArgs a{};
     a.has_hue = hue != 0; a.hue_half = 0.5 * (double)std::min(std::max(hue, -360), 360);
@@ -1943,8 +1942,42 @@ int havc_image_chroma_tweak(havc_ctx* c, const uint8_t* img, uint8_t* out, int w
     a.has_hue2 = adj_hue != 0; a.hue_half2 = 0.5 * (double)std::min(std::max(adj_hue, -360), 360);
     a.has_sat2 = adj_sat != 1.0; a.sat2c = clampd(adj_sat, 0.0, 10.0);
     a.weight = adj_weight;
+    return a;
+}
+
+int havc_image_chroma_tweak(havc_ctx* c, const uint8_t* img, uint8_t* out, int width, int height, double sat, double bright, int hue,
+                            int has_adjust, const double* hue_ranges, int n_ranges, double adj_sat, int adj_hue, double adj_weight) {
+    if (!c || !img || !out || width <= 0 || height <= 0 || n_ranges < 0 || n_ranges > HAVC_MAX_HUE_RANGES || (has_adjust && (!hue_ranges || n_ranges < 1)))
+        return fail(c, HAVC_E_INVALID, "image_chroma_tweak: bad args (1..8 hue ranges with an adjust stage)");
+    const ChromaTweakArgs a = chroma_tweak_args(sat, bright, hue, has_adjust, hue_ranges, n_ranges, adj_sat, adj_hue, adj_weight);
     return run_filter(c, img, nullptr, out, (size_t)width * height * 3, "image_chroma_tweak", [&](const uint8_t* da, const uint8_t*, uint8_t* dout) {
         return launch_chroma_tweak(da, dout, (int64_t)width * height, a, c->stream); });
+}
+
+int havc_stabilizer_chain(havc_ctx* c, const uint8_t* img, uint8_t* out, int width, int height, const havc_stab_stage* stages, int n_stages) {
+    if (!c || !img || !out || width <= 0 || height <= 0 || n_stages < 0 || n_stages > HAVC_MAX_STAB_STAGES || (n_stages && !stages))
+        return fail(c, HAVC_E_INVALID, "stabilizer_chain: bad args (0..3 stages)");
+    StabChainArgs a{};
+    a.n = n_stages;
+    for (int i = 0; i < n_stages; ++i) {
+        const havc_stab_stage& s = stages[i];
+        if (s.kind < 0 || s.kind > 1 || s.merge_mode < -1 || s.merge_mode > 3 || s.n_ranges < 0 || s.n_ranges > HAVC_MAX_HUE_RANGES ||
+            (s.kind == 1 && (s.has_adjust < 0 || s.has_adjust > 1 || (s.has_adjust && s.n_ranges < 1))))
+            return fail(c, HAVC_E_INVALID, "stabilizer_chain: bad stage (kind 0 / 1, merge_mode -1..3, at most 8 hue ranges, 1..8 with an adjust stage)");
+        StabStage& d = a.st[i];
+        d.kind = s.kind; d.identity = s.kind == 1 && s.identity; d.merge_mode = s.merge_mode; d.tresh = s.tresh; d.grad = s.grad;
+        if (s.kind == 0) {
+            d.tw.hue_offset = s.hue_offset; d.tw.brightness = s.brightness; d.tw.contrast = 1.f; d.tw.color = s.color; d.tw.mean_l = 0;
+            d.tw.n_ranges = s.n_ranges;
+            for (int k = 0; k < s.n_ranges; ++k) { d.tw.range_lo[k] = s.hue_ranges[2 * k]; d.tw.range_hi[k] = s.hue_ranges[2 * k + 1]; }
+        } else {
+            d.ct = chroma_tweak_args(s.sat, s.bright, s.hue, s.has_adjust, s.hue_ranges, s.n_ranges, s.adj_sat, s.adj_hue, s.adj_weight);
+        }
+    }
+    const size_t nb = (size_t)width * height * 3;
+    return run_filter(c, img, nullptr, out, nb, "stabilizer_chain", [&](const uint8_t* da, const uint8_t*, uint8_t* dout) {
+        if (a.n == 0) return da == dout ? 0 : (int)hipMemcpyAsync(dout, da, nb, hipMemcpyDeviceToDevice, c->stream);
+        return launch_stabilizer_chain(da, dout, (int64_t)width * height, a, c->stream); });
 }
 
 int havc_luma_lut(havc_ctx* c, const uint8_t* img, const uint8_t* lut256, uint8_t* out, int width, int height) {

@@ -156,6 +156,19 @@ struct ChromaTweakArgs {
 };
 int launch_chroma_tweak(const uint8_t* img, uint8_t* out, int64_t npix, const ChromaTweakArgs& a, hipStream_t s);
 int launch_luma_lut(const uint8_t* img, const uint8_t* d_lut, uint8_t* out, int64_t npix, hipStream_t s);
+// stabilizer.hip: the HAVC_stabilizer filter chain (dark tweak -> chroma / bright tweak -> colormap) in ONE launch.  A stage = one of the two tweaks above
+// followed by a luma-masked merge with the stage's input (the operands of launch_luma_merge; merge_mode -1: the tweaked pixel as it is).
+#define HAVC_MAX_STAB_STAGES 3
+struct StabStage {
+    int kind;                     // 0 = image_tweak (tw), 1 = image_chroma_tweak (ct)
+    int identity;                 // kind 1: the tweak hands its input on (np_image_chroma_tweak's early return); the merge still runs
+    int merge_mode;               // -1 none, 0..3 = launch_luma_merge's modes
+    double tresh, grad;
+    TweakArgs tw;
+    ChromaTweakArgs ct;
+};
+struct StabChainArgs { int n; StabStage st[HAVC_MAX_STAB_STAGES]; };
+int launch_stabilizer_chain(const uint8_t* img, uint8_t* out, int64_t npix, const StabChainArgs& a, hipStream_t s);
 int launch_restore_color_gradient(const uint8_t* color, const uint8_t* gray, uint8_t* out, int64_t npix, double sat, int tht, double alpha,
                                   double weight, int algo, int return_mask, hipStream_t s);
 // separable polyphase resample of interleaved u8 RGB (tap tables from the host; Spline64 = harness stand-in
@@ -197,6 +210,7 @@ void preload_zhang();
 void preload_attention();
 void preload_colorfilters();
 void preload_tweaks();
+void preload_stabilizer();
 void preload_ddcolor();
 void preload_colormnet();
 void preload_colormnet_net();

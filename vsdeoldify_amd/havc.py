@@ -2,6 +2,7 @@
 
     HAVC_colorizer   vsdeoldify/__init__.py:2290-2523     HAVC_merge       vsdeoldify/__init__.py:2536-2675
     HAVC_ddeoldify   vsdeoldify/__init__.py:3612-3628     ddeoldify        vsdeoldify/__init__.py:3642-3653
+    HAVC_stabilizer  vsdeoldify/__init__.py:2748-2873
 
 Same names, argument lists, defaults, parameter normalisation, frame-size rule, model routing, combine dispatch
 (vsslib/mcomb.py:125-192) and error texts; a "clip" is a uint8 array [n, h, w, 3] (or one frame [h, w, 3], or a
@@ -9,7 +10,7 @@ Same names, argument lists, defaults, parameter normalisation, frame-size rule, 
 behind `HAVC_colorizer` (models and nets are built once and reused between calls).
 
 What only VapourSynth can do stays there and is REFUSED here instead of being approximated: `vs_tweak` (deoldify / ddcolor
-sat / hue other than 1 / 0, `luma_mask_sat` < 1), scene detection (`sc_threshold` > 0, `sc_min_freq` > 0), the parts of the DDColor
+sat / hue other than 1 / 0, `luma_mask_sat` < 1), the temporal half of HAVC_stabilizer (`stab=True`), scene detection (`sc_threshold` > 0, `sc_min_freq` > 0), the parts of the DDColor
 pre-tweaks that are VapourSynth filters (`ddtweak`: bright / cont / gamma through vs_tweak, rgb_denoise, retinex), non-RGB24 formats.
 Computed here: the hue adjustment vs_sc_ddcolor applies to every DDColor frame (default "300:360|0.8,0.1") and the luma-constrained
 pre-tweak with its luma recovery (HAVCFrameColorizer._read_ddtweak).  zimg's Spline64 is replaced by the library's own Spline64 (outside the parity
@@ -434,3 +435,69 @@ def HAVC_merge(clipa=None, clipb=None, clip_luma=None, weight=0.5, method=2, cmc
     if clip_luma is not None:                                                                     # __init__.py:2673-2676
         merged = _clip_chroma_resize(clip_luma, merged, device_index)
     return done(merged)
+
+
+# ---- HAVC_stabilizer (vsdeoldify/__init__.py:2748-2873) ----------------------------------------------------------------------------------------
+_COLORMAPS = ['none', 'blue->brown', 'blue->red', 'blue->green', 'green->brown', 'green->red', 'green->blue', 'redrose->brown', 'redrose->blue',
+              'red->brown', 'red->blue', 'yellow->rose']                                          # havc_utils.py:564-565
+_COLORMAP_HUES = ["none", "180:280|+140", "180:280|+100", "180:280|+220", "80:180|+260", "80:180|+220", "80:180|+140", "300:360,0:20|+40",
+                  "300:360,0:20|+260", "320:360|+50", "300:360|+260", "30:90|+300"]               # havc_utils.py:566-567
+
+
+def _get_colormap(colormap):
+    """havc_utils._get_colormap(ColorMap) with its default ColorTune = "light" (havc_utils.py:552-581): a known name -> its "chroma adjustment" with
+    weight 0.90; a string parse_hue_adjust accepts is handed on; anything else is an error"""
+    colormap = colormap.lower()
+    if colormap in _COLORMAPS:
+        return _COLORMAP_HUES[_COLORMAPS.index(colormap)] + "," + "0.90"
+    if F.parse_hue_adjust(colormap) is None:
+        raise HAVCError("HAVC_main: ColorMap choice is invalid for '" + colormap + "'")           # havc_utils.py:575
+    return colormap
+
+
+def _stabilizer_frame_size(render_factor, width):
+    """__init__.py:2795-2803 -> (render_factor, frame_size)"""
+    if render_factor != 0 and render_factor not in range(16, 65):
+        raise HAVCError("HAVC_stabilizer: render_factor must be between: 16-64")                  # __init__.py:2795-2796
+    if render_factor == 0:
+        render_factor = min(max(math.trunc(0.4 * width / 16), 16), 32)                            # __init__.py:2798-2799
+    return render_factor, min(render_factor * 16, width)                                          # __init__.py:2803
+
+
+def HAVC_stabilizer(clip, dark=False, dark_p=(0.2, 0.8), smooth=False, smooth_p=(0.3, 0.7, 0.9, 0.0, "none"), stab=False,
+                    stab_p=(5, 'A', 1, 15, 0.2, 0.8), colormap="none", render_factor=24, device_index=0):
+    """vsdeoldify/__init__.py:2748-2751: the colour filters every HAVC_main preset ends in, at reduced resolution -- Spline64 squash to
+    frame_size x frame_size (the library's Spline64, the stand-in of zimg's everywhere in this file), dark -> smooth -> colormap in ONE launch
+    (stabilizer.stabilize_np), Spline64 back + the luma of the source (_clip_chroma_resize).  ndarray in -> ndarray out; DeviceImage in -> DeviceImage out
+    (nothing leaves HBM, the call only enqueues).  stab=True is refused: see below."""
+    if clip is None or not (is_device(clip) or isinstance(clip, np.ndarray)):
+        raise HAVCError("HAVC_stabilizer: this is not a clip")
+    if stab:                                                                                      # __init__.py:2862-2866
+        raise NotImplementedError("HAVC_stabilizer(stab=True): vs_chroma_stabilizer_ex is VapourSynth glue -- a zimg YUV420P8 round trip with error-diffusion "
+                                  "dither, std.AverageFrames driven by scene-change props and the ReduceFlicker plugin (vsfilters.py:84-115, 216-242): "
+                                  "not in this harness")
+    clip, single = _as_clip(clip)
+    n, h, w, _ = clip.shape
+    _, fs = _stabilizer_frame_size(render_factor, w)
+    dark_args = smooth_args = None
+    if dark:                                                                                      # __init__.py:2806-2813, 2850-2852
+        dark_args = (dark_p[0], dark_p[1], (dark_p[2] if len(dark_p) > 2 else "none").lower())
+    if smooth:                                                                                    # __init__.py:2815-2824, 2854-2857
+        smooth_args = (smooth_p[0], smooth_p[1], smooth_p[2], -smooth_p[3], (smooth_p[4] if len(smooth_p) > 4 else "none").lower())
+    colormap = colormap.lower()                                                                   # __init__.py:2827-2832
+    colormap_adjust = _get_colormap(colormap) if colormap not in ("none", "") else None
+    if colormap_adjust is not None:
+        # _get_colormap hands on ANY string without a "|" ("purple->green"); the reference then dies in the first frame's selector, inside
+        # _parse_hue_range (restcolor.py:436-470).  Same refusal, raised here, before anything is enqueued.
+        try:
+            F.parse_hue_ranges(F.parse_hue_adjust(colormap_adjust)[0])
+        except ValueError:
+            raise HAVCError("HAVC_main: ColorMap choice is invalid for '" + colormap + "'") from None
+    from .stabilizer import stabilize_np
+    ctx = get_context(device_index)
+    sq = spline64(ctx, clip, fs, fs)                                                              # __init__.py:2804
+    col = stabilize_np(ctx, sq, dark_args, smooth_args, colormap_adjust)
+    out = _clip_chroma_resize(clip, col, device_index)                                            # __init__.py:2868-2869: even when every filter is off
+    if single:
+        return out.reshaped(out.shape[1:]) if is_device(out) else out[0]
+    return out
