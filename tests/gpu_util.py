@@ -108,6 +108,20 @@ def conv_op_precise(ctx, x, W, bias=None, scale=None, shift=None, stride=1, pad=
     return hl_unpack(raw, yv.C), raw
 
 
+def generator_runtime(ctx, sd, arch, precision=None):
+    """GeneratorRuntime of a seeded state dict for tests that run one test body in both arithmetics: None = the session's mode, packed per test as
+    always; "fast" / "precise" = that mode, on the session's shared packed blob of (state dict, mode) where HAVC_SHARE_WEIGHTS is on (a precise pack
+    costs ~20 s of host time; render.ModelImageRender._runtime shares under the same key)"""
+    import os
+    from vsdeoldify_amd.render import GeneratorRuntime
+    if precision is None:
+        return GeneratorRuntime(ctx, sd, arch)
+    share = ("sd", id(sd)) if os.environ.get("HAVC_SHARE_WEIGHTS", "0") != "0" else None
+    rt = GeneratorRuntime(ctx, sd, arch, share_key=share, precision=precision)
+    assert rt.gen.precise == (precision == "precise")
+    return rt
+
+
 # ---- shared CPU-oracle frames (round 6: the suite evaluated the same 1080p oracle frame in several files, ~5 s each) ----
 _ORACLE_FULLSIZE = {}
 

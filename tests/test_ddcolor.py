@@ -221,19 +221,27 @@ def test_gpu_dwconv7_layernorm_fused_kernel(ctx, C, H, W, B):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("S", [32, 96])
-def test_gpu_ddcolor_frames_do_not_depend_on_the_batch(ctx, S):
+@pytest.mark.parametrize("S,precision", [pytest.param(32, "fast", id="32"), pytest.param(96, "fast", id="96"),
+                                         pytest.param(32, "precise", id="32-precise"), pytest.param(96, "precise", id="96-precise")])
+def test_gpu_ddcolor_frames_do_not_depend_on_the_batch(ctx, S, precision):
     """A frame colours identically alone and inside a batch, also where a 256-pixel GEMM tile of the folded tail spans several frames
     (S = 32: 64 low-res pixels per frame, four frames per tile; S = 96: 576 pixels, tiles straddle frame boundaries) and where the fused
     block head sees 1 x 1 and 3 x 3 feature maps."""
-    from vsdeoldify_amd.ddcolor import DDColorRuntime
+    from vsdeoldify_amd.ddcolor import DDColorRender, DDColorRuntime
     sd = synth_ddcolor_state_dict(4, **SMALL)
-    rt = DDColorRuntime(ctx, sd, **SMALL)
+    if precision == "precise":            # the default mode through the public entry: DDColorRender(precision="precise").colorize_frames
+        dd = DDColorRender(model=1, input_size=S, state_dict=sd, precision="precise", **SMALL)
+        assert dd.precision == "precise"
+        rt, colorize = dd.rt, (lambda f, max_batch: dd.colorize_frames(f, max_batch=max_batch))
+    else:                                 # (DDColorRuntime's own default is "fast": the existing cases are unchanged)
+        rt = DDColorRuntime(ctx, sd, **SMALL)
+        colorize = rt.colorize
     try:
+        assert rt.gen.precise == (precision == "precise")
         r = np.random.default_rng(S)
         frames = r.integers(0, 256, (5, S, S, 1), dtype=np.uint8).repeat(3, -1)
-        together = rt.colorize(frames, max_batch=5)
-        alone = np.stack([rt.colorize(frames[i:i + 1], max_batch=1)[0] for i in range(5)])
+        together = colorize(frames, max_batch=5)
+        alone = np.stack([colorize(frames[i:i + 1], max_batch=1)[0] for i in range(5)])
         assert np.array_equal(together, alone)
         want = np.stack([D.colorize_frame(sd, f, **SMALL) for f in frames[:2]])
         d = np.abs(together[:2].astype(int) - want.astype(int))
@@ -244,6 +252,15 @@ def test_gpu_ddcolor_frames_do_not_depend_on_the_batch(ctx, S):
 
 @pytest.mark.gpu
 def test_gpu_ddcolor_coalesced_per_frame_calls(ctx, monkeypatch):
+    _ddcolor_coalesced_per_frame_calls(monkeypatch, None)
+
+
+@pytest.mark.gpu
+def test_gpu_ddcolor_coalesced_per_frame_calls_precise(ctx, monkeypatch):
+    _ddcolor_coalesced_per_frame_calls(monkeypatch, "precise")
+
+
+def _ddcolor_coalesced_per_frame_calls(monkeypatch, precision):
     """colorize_frame from several threads through one DDColorRender(coalesce=N): the calls are merged into batches and every caller
     gets the bytes of a call of its own (a DDColor pass costs 7.7 ms alone and 1.2 ms per frame in a batch of 16)."""
     import threading
@@ -254,9 +271,10 @@ def test_gpu_ddcolor_coalesced_per_frame_calls(ctx, monkeypatch):
     start = threading.Barrier(T)
     r = np.random.default_rng(3)
     frames = [r.integers(0, 256, (S, S, 1), dtype=np.uint8).repeat(3, -1) for _ in range(T * K)]
-    ref = DDColorRender(model=1, input_size=S, state_dict=sd, **SMALL)
-    shared = DDColorRender(model=1, input_size=S, state_dict=sd, coalesce=T, **SMALL)
+    ref = DDColorRender(model=1, input_size=S, state_dict=sd, precision=precision, **SMALL)
+    shared = DDColorRender(model=1, input_size=S, state_dict=sd, coalesce=T, precision=precision, **SMALL)
     try:
+        assert precision is None or ref.rt.gen.precise == shared.rt.gen.precise == (precision == "precise")
         want = [ref.colorize_frame(f) for f in frames]
         got, errs = {}, []
 

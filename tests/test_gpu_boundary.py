@@ -34,14 +34,22 @@ def test_planar_interleave_round_trip(ctx):
         assert all(np.array_equal(back[p], rgb[:, :, p]) for p in range(3))            # np_array_to_frame
 
 
-@pytest.mark.parametrize("modelname", ["video", "stable"])
-def test_planar_frame_entry_equals_the_image_entry(ctx, modelname):
+def _precise_is(render, precision):
+    """a render asked for a mode really runs it (precision=None: the session's mode, whatever it is)"""
+    return precision is None or all(rt.gen.precise == (precision == "precise") for rt in (render._video, render._second) if rt is not None)
+
+
+# (existing cases keep their ids and the session's mode; the "-precise" cases run the package default arithmetic)
+@pytest.mark.parametrize("modelname,precision", [pytest.param("video", None, id="video"), pytest.param("stable", None, id="stable"),
+                                                 pytest.param("video", "precise", id="video-precise"), pytest.param("stable", "precise", id="stable-precise")])
+def test_planar_frame_entry_equals_the_image_entry(ctx, modelname, precision):
     """vs_sc_deoldify's selector body (frame_to_image -> get_transformed_image -> image_to_frame) on planes with a stride"""
     from PIL import Image
     from tests.test_gpu_deoldify import make_frame
     from vsdeoldify_amd.render import ModelImageRender
     sds = {"video": synth_state_dict("wide", 1), "stable": synth_state_dict("wide", 2)}
-    r = ModelImageRender(None, modelname, 4, 0.5, state_dicts=sds)
+    r = ModelImageRender(None, modelname, 4, 0.5, state_dicts=sds, precision=precision)
+    assert _precise_is(r, precision)
     img = make_frame(64, 77)
     want = np.asarray(r.get_transformed_image(Image.fromarray(img)))
     got = r.get_transformed_planes(_planes(img, 128), _planes(np.zeros_like(img), 96))
@@ -53,10 +61,16 @@ def test_planar_frame_entry_equals_the_image_entry(ctx, modelname):
 def test_ddcolor_rgbs_rgbh_call_shape(ctx):
     """vsddcolor.ddcolor is called with an RGBH / RGBS clip (vsslib/vsmodels.py:353-363): float planes in, float planes out,
     quantised to RGB24 afterwards by zimg.  Same colours as the u8 entry (which truncates x * 255): floor(out * 255) == u8."""
+    ddcolor_rgbs_rgbh_call_shape(None)
+
+
+def ddcolor_rgbs_rgbh_call_shape(precision):
+    """body of the test above; tests/test_gpu_default_mode.py runs it with precision="precise" """
     from vsdeoldify_amd.ddcolor import DDColorRender
     from vsdeoldify_amd.synth import synth_ddcolor_state_dict
     small = dict(depths=(1, 1, 2, 1), dec_layers=3)
-    dd = DDColorRender(1, 64, 0, state_dict=synth_ddcolor_state_dict(1, **small), **small)
+    dd = DDColorRender(1, 64, 0, state_dict=synth_ddcolor_state_dict(1, **small), precision=precision, **small)
+    assert precision is None or dd.rt.gen.precise == (precision == "precise")
     r = np.random.default_rng(3)
     frame = np.clip(r.normal(120, 50, (64, 64, 1)), 0, 255).astype(np.uint8).repeat(3, -1)
     u8 = dd.colorize_frame(frame)
@@ -114,13 +128,15 @@ def test_device_operands_match_host_operands(ctx):
         F.image_luma_np(ctx, dstack_)                       # frame-level statistic: one frame at a time
 
 
-@pytest.mark.parametrize("pinned", [True, False])
-def test_pipelined_host_clip_equals_resident_clip(ctx, pinned):
+@pytest.mark.parametrize("pinned,precision", [pytest.param(True, None, id="True"), pytest.param(False, None, id="False"),
+                                              pytest.param(True, "precise", id="True-precise"), pytest.param(False, "precise", id="False-precise")])
+def test_pipelined_host_clip_equals_resident_clip(ctx, pinned, precision):
     """havc_colorize_clip_host (three streams, double-buffered staging) == havc_colorize_clip on the same frames; 5 frames in
     batches of 2 exercise both staging slots and a ragged last batch."""
     from vsdeoldify_amd.clip import ClipColorizer, synthetic_gray_frame
     sds = {"video": synth_state_dict("wide", 1), "stable": synth_state_dict("wide", 2)}
-    cc = ClipColorizer("stable", 6, 0.5, device_index=0, state_dicts=sds, max_batch=2)
+    cc = ClipColorizer("stable", 6, 0.5, device_index=0, state_dicts=sds, max_batch=2, precision=precision)
+    assert _precise_is(cc.render, precision)
     frames = np.stack([synthetic_gray_frame(i, 320, 180) for i in range(5)])
     want = cc.colorize(frames)
     if pinned:
@@ -139,6 +155,14 @@ def test_pipelined_host_clip_equals_resident_clip(ctx, pinned):
 
 
 def test_worker_contexts_run_concurrently_and_share_weights(ctx):
+    _worker_contexts_run_concurrently_and_share_weights(ctx, None)
+
+
+def test_worker_contexts_run_concurrently_and_share_weights_precise(ctx):
+    _worker_contexts_run_concurrently_and_share_weights(ctx, "precise")
+
+
+def _worker_contexts_run_concurrently_and_share_weights(ctx, precision):
     """VERDICT r1 #10 / SURVEY §5: VapourSynth calls the selector from several worker threads.  One context per worker (own mutex,
     streams, workspace, activation arena), ONE packed weight blob per device: two threads colour different frames at the same
     time and get exactly what a single thread gets; the second worker adds activations but no second copy of the weights."""
@@ -149,9 +173,10 @@ def test_worker_contexts_run_concurrently_and_share_weights(ctx):
     from vsdeoldify_amd.render import ModelImageRender
     sds = {"video": synth_state_dict("wide", 1), "stable": synth_state_dict("wide", 2)}
     frames = [make_frame(64, 200 + i) for i in range(6)]
-    ref = ModelImageRender(None, "stable", 4, 0.5, state_dicts=sds)
+    ref = ModelImageRender(None, "stable", 4, 0.5, state_dicts=sds, precision=precision)
     want = [np.asarray(ref.get_transformed_image(Image.fromarray(f))) for f in frames]
-    workers = [ModelImageRender(None, "stable", 4, 0.5, state_dicts=sds, worker=w) for w in (1, 2)]
+    workers = [ModelImageRender(None, "stable", 4, 0.5, state_dicts=sds, worker=w, precision=precision) for w in (1, 2)]
+    assert all(_precise_is(r, precision) for r in [ref] + workers)
     assert workers[0].ctx is not workers[1].ctx and workers[0].ctx is not ctx
     assert workers[0]._video.weights is workers[1]._video.weights                   # shared blob
     w_bytes = len(workers[0]._video.gen.blob) + len(workers[0]._second.gen.blob)
@@ -174,8 +199,8 @@ def test_worker_contexts_run_concurrently_and_share_weights(ctx):
     assert all(np.array_equal(got[i], want[i]) for i in range(6))
 
 
-@pytest.mark.parametrize("coalesce", [6, 2])
-def test_coalesced_per_frame_calls_match_separate_calls(ctx, coalesce, monkeypatch):
+@pytest.mark.parametrize("coalesce,precision", [pytest.param(6, None, id="6"), pytest.param(2, None, id="2"), pytest.param(6, "precise", id="6-precise")])
+def test_coalesced_per_frame_calls_match_separate_calls(ctx, coalesce, precision, monkeypatch):
     """The reference's call shape is ONE get_transformed_image per frame from each VapourSynth worker thread.  A render built with
     coalesce=N merges the concurrent calls of N threads into batches (havc_batcher): every caller gets exactly the bytes of a call of
     its own, and fewer batches than calls were run."""
@@ -188,9 +213,10 @@ def test_coalesced_per_frame_calls_match_separate_calls(ctx, coalesce, monkeypat
     T, K = 6, 4
     start = threading.Barrier(T)
     frames = [make_frame(64, 300 + i) for i in range(T * K)]
-    ref = ModelImageRender(None, "stable", 4, 0.5, state_dicts=sds)
+    ref = ModelImageRender(None, "stable", 4, 0.5, state_dicts=sds, precision=precision)
     want = [np.asarray(ref.get_transformed_image(Image.fromarray(f))) for f in frames]
-    shared = ModelImageRender(None, "stable", 4, 0.5, state_dicts=sds, coalesce=coalesce)      # 2: more caller threads than a batch holds
+    shared = ModelImageRender(None, "stable", 4, 0.5, state_dicts=sds, coalesce=coalesce, precision=precision)      # 2: more caller threads than a batch holds
+    assert _precise_is(ref, precision) and _precise_is(shared, precision)
     got, errs = {}, []
 
     def run(t):

@@ -105,8 +105,17 @@ def test_model_image_render_nonsquare(ctx, sds):
 
 
 def test_batch_matches_single(ctx, sds):
+    _batch_matches_single(ctx, sds, None)
+
+
+def test_batch_matches_single_precise(ctx, sds):
+    _batch_matches_single(ctx, sds, "precise")
+
+
+def _batch_matches_single(ctx, sds, precision):
     """frames are independent: a batch of 3 must equal three single-frame calls bit for bit."""
-    rt = GeneratorRuntime(ctx, sds["video"], "wide")
+    from tests.gpu_util import generator_runtime
+    rt = generator_runtime(ctx, sds["video"], "wide", precision)
     try:
         frames = np.stack([make_frame(64, s) for s in (1, 2, 3)])
         assert np.array_equal(raw_gpu(ctx, rt, frames), np.concatenate([raw_gpu(ctx, rt, f[None]) for f in frames]))

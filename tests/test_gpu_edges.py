@@ -41,10 +41,18 @@ def test_extreme_pixel_values(ctx):
 
 
 def test_empty_and_ragged_batches(ctx):
+    _empty_and_ragged_batches(ctx, None)
+
+
+def test_empty_and_ragged_batches_precise(ctx):
+    _empty_and_ragged_batches(ctx, "precise")
+
+
+def _empty_and_ragged_batches(ctx, precision):
     """0 frames is a no-op; 5 frames through a max_batch-2 net = 2 + 2 + 1 and equals frame-by-frame results"""
-    from vsdeoldify_amd.render import GeneratorRuntime
+    from tests.gpu_util import generator_runtime
     from vsdeoldify_amd.synth import synth_state_dict
-    rt = GeneratorRuntime(ctx, synth_state_dict("wide", 1), "wide")
+    rt = generator_runtime(ctx, synth_state_dict("wide", 1), "wide", precision)
     try:
         net = rt.net(64, 2)
         frames = np.stack([_rgb(64, 64, s)[:, :, :1].repeat(3, -1) for s in range(5)])
@@ -86,6 +94,14 @@ def test_bad_arguments_are_refused_not_crashed(ctx):
 
 
 def test_oom_returns_gray_input_like_the_reference(ctx, monkeypatch):
+    _oom_returns_gray_input_like_the_reference(monkeypatch, None)
+
+
+def test_oom_returns_gray_input_like_the_reference_precise(ctx, monkeypatch):
+    _oom_returns_gray_input_like_the_reference(monkeypatch, "precise")
+
+
+def _oom_returns_gray_input_like_the_reference(monkeypatch, precision):
     """deoldify/filters.py:55-63: on an out-of-memory error _model_process logs a warning and returns the (squared, gray) model
     image -- and filter() CONTINUES with it (un-square to the source size, post-process), so the caller still gets an image of
     the source size."""
@@ -93,7 +109,8 @@ def test_oom_returns_gray_input_like_the_reference(ctx, monkeypatch):
     from oracle import pipeline
     from vsdeoldify_amd import render
     from vsdeoldify_amd.synth import synth_state_dict
-    mir = render.ModelImageRender("", "video", render_factor=4, state_dicts={"video": synth_state_dict("wide", 1)})
+    mir = render.ModelImageRender("", "video", render_factor=4, state_dicts={"video": synth_state_dict("wide", 1)}, precision=precision)
+    assert precision is None or mir._video.gen.precise == (precision == "precise")
     img = Image.fromarray(_rgb(48, 80, 3))
     assert mir.get_transformed_image(img).size == img.size
 
@@ -106,7 +123,7 @@ def test_oom_returns_gray_input_like_the_reference(ctx, monkeypatch):
         want = pipeline.post_process(np.asarray(gray.resize(im.size, resample=Image.BILINEAR)), np.asarray(im))
         assert got.size == im.size and np.array_equal(np.asarray(got), want)
     with pytest.raises(FileNotFoundError):
-        render.ModelImageRender("/nonexistent", "video", render_factor=4)
+        render.ModelImageRender("/nonexistent", "video", render_factor=4, precision=precision)
 
 
 def test_stream_recreation_is_refused_once_a_handle_is_out():

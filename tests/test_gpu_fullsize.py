@@ -109,18 +109,35 @@ def test_conv_frame_chunking_is_bit_identical():
     """Convs whose operands exceed one buffer descriptor run as several frame chunks (havc_runtime.cpp run_op; batch >= 23 at
     560x560).  HAVC_DESC_LIMIT_BYTES lowers the limit of a NEW context so that a 3-frame batch at 96x96 is issued frame by frame
     for the big layers; the bytes must equal the single-launch result."""
+    _conv_frame_chunking(str(96 * 96 * 320 * 2 + 4096), None)    # one frame of the 320-pitch tail buffer (+ slack) per launch
+
+
+def test_conv_frame_chunking_is_bit_identical_precise(ctx):
+    """the same in the default mode: precise pixel rows are twice as wide (hi | lo), so chunking sets in at half the batch; the lowered limit is one
+    frame of the PRECISE plan's own tail buffer (+ slack), read from the plan"""
+    rt = gu.generator_runtime(ctx, synth_state_dict("wide", 1), "wide", "precise")      # the session's packed precise generator; only its plan is needed here
+    gen = rt.gen
+    rt.close()
+    ops, _, _, _, names = gen.plan(96)
+    tail_pitch = int(ops[names.index("layers.10.layers.0.0")]["dst_cpitch"])
+    assert gen.precise and tail_pitch == 2 * 320
+    _conv_frame_chunking(str(96 * 96 * tail_pitch * 2 + 4096), gen)
+
+
+def _conv_frame_chunking(limit_bytes, generator):
     sd = synth_state_dict("wide", 1)
     frames = np.stack([make_frame(96, s) for s in (21, 22, 23)])
     outs = []
-    for limit in (None, str(96 * 96 * 320 * 2 + 4096)):          # one frame of the 320-pitch tail buffer (+ slack) per launch
+    for limit in (None, limit_bytes):
         if limit:
             os.environ["HAVC_DESC_LIMIT_BYTES"] = limit
         try:
             c = nat.Context(0)
         finally:
             os.environ.pop("HAVC_DESC_LIMIT_BYTES", None)
-        rt = GeneratorRuntime(c, sd, "wide")
+        rt = GeneratorRuntime(c, sd, "wide") if generator is None else GeneratorRuntime(c, None, "wide", generator=generator, precision="precise")
         try:
+            assert generator is None or all(int(o["flags"]) & nat.F_PRECISE for o in rt.net(96, 3).ops)
             c.reset_stats()
             outs.append((raw_gpu(c, rt, frames), c.stats().launches))
         finally:

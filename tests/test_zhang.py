@@ -135,6 +135,15 @@ def test_gpu_model_colorization_frame(ctx, model, hw):
 
 @gpu
 def test_gpu_model_colorization_coalesced_calls(ctx, monkeypatch):
+    _model_colorization_coalesced_calls(monkeypatch, None)
+
+
+@gpu
+def test_gpu_model_colorization_coalesced_calls_precise(ctx, monkeypatch):
+    _model_colorization_coalesced_calls(monkeypatch, "precise")
+
+
+def _model_colorization_coalesced_calls(monkeypatch, precision):
     """colorize_frame from several threads through ModelColorization(coalesce=N): merged into batches (havc_batcher kind 2), every caller
     gets the bytes of a call of its own."""
     import threading
@@ -143,10 +152,12 @@ def test_gpu_model_colorization_coalesced_calls(ctx, monkeypatch):
     start = threading.Barrier(4)
     sd = synth_zhang_state_dict("eccv16", 9)
     imgs = [frame(120, 160, 300 + i) for i in range(8)]
-    mc = ModelColorization("eccv16", True, state_dict=sd)
+    mc = ModelColorization("eccv16", True, state_dict=sd, precision=precision)
+    assert precision is None or mc.gen.precise == (precision == "precise")
     want = [mc.colorize_frame(im) for im in imgs]
     mc.close()
-    mc = ModelColorization("eccv16", True, state_dict=sd, coalesce=4)
+    mc = ModelColorization("eccv16", True, state_dict=sd, coalesce=4, precision=precision)
+    assert precision is None or mc.gen.precise == (precision == "precise")
     got, errs = {}, []
 
     def run(t):

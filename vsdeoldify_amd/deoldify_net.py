@@ -80,6 +80,15 @@ class DeoldifyGenerator:
             np.savez(f, blob=np.frombuffer(self.blob, dtype=np.uint8), meta=np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8))
 
     @classmethod
+    def stored_precision(cls, path):
+        """"fast" / "precise": the arithmetic the blob at `path` was packed for (reads the meta record only, not the blob)"""
+        import json
+        meta = json.loads(bytes(np.load(path)["meta"]).decode())
+        if meta.get("format") != cls.FORMAT:
+            raise ValueError(f"{path}: not a {cls.FORMAT} file")
+        return meta.get("precision", "fast")
+
+    @classmethod
     def load(cls, path):
         """Inverse of save(): no packing work, the plan emitter runs on a shape-only skeleton of the state dict."""
         import json

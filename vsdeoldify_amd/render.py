@@ -38,7 +38,12 @@ def get_context(device_index=0, worker=0):
     return _contexts[key]
 
 
-_weights_cache = {}          # (device, arch, fusion flags, id of the state dict / path) -> (generator, device weights)
+_weights_cache = {}          # (device, arch, fusion flags, id of the state dict / path, precision) -> (generator, device weights)
+
+
+def _share_key(arch, fuse_final, fuse_blur, share_key, precision):
+    """cache key of a packed model below the device: the precision is ALWAYS part of it -- a fast and a precise render on the same files never share a blob"""
+    return (arch, fuse_final, fuse_blur) + tuple(share_key) + (precision,)
 
 
 def _shared_weights(ctx, key, make_generator):
@@ -48,6 +53,28 @@ def _shared_weights(ctx, key, make_generator):
         gen = make_generator()
         _weights_cache[full] = (gen, nat.Weights(ctx, gen.blob))
     return _weights_cache[full]
+
+
+def choose_weight_file(path, packed, precision):
+    """Which file a model is read from: -> ("havc", packed) or ("pth", path).  The packed blob of tools/convert_weights.py is used only when it holds
+    the requested arithmetic (its stored "precision" field) and is not older than the .pth next to it; otherwise the .pth is packed in the requested mode.
+    A file under the blob's name that is no readable blob counts as absent while a .pth is there.  A deployment that ships only a blob of the OTHER mode cannot be served: FileNotFoundError that says which mode the blob holds and which was asked for."""
+    have_pth = os.path.isfile(path)
+    stored = None
+    if os.path.isfile(packed):
+        try:
+            stored = DeoldifyGenerator.stored_precision(packed)
+        except Exception:                 # not a packed model (a stray or truncated file): absent as long as the .pth can serve, an error of its own otherwise
+            if not (have_pth and os.path.getsize(path) > 0):
+                raise
+    if stored == precision and (not have_pth or os.path.getmtime(packed) >= os.path.getmtime(path)):
+        return "havc", packed
+    if have_pth and os.path.getsize(path) > 0:
+        return "pth", path
+    if stored is not None and stored != precision:
+        raise FileNotFoundError(f"DeOldify weights not found: {path}; {packed} holds a {stored!r} blob but precision={precision!r} was asked for "
+                                f"(convert the checkpoint with tools/convert_weights.py --precision {precision}, or ship the .pth)")
+    raise FileNotFoundError(f"DeOldify weights not found: {path}")
 
 
 def _load_pth(path):
@@ -62,7 +89,7 @@ class GeneratorRuntime:
     def __init__(self, ctx, state_dict, arch, fuse_final=True, fuse_blur=True, generator=None, share_key=None, precision="fast"):
         self.ctx, self.arch = ctx, arch
         if share_key is not None:              # worker contexts of one device: one packed blob for all of them
-            self.gen, self.weights = _shared_weights(ctx, (arch, fuse_final, fuse_blur) + tuple(share_key) + ((precision,) if precision != "fast" else ()),
+            self.gen, self.weights = _shared_weights(ctx, _share_key(arch, fuse_final, fuse_blur, share_key, precision),
                                                      lambda: generator or DeoldifyGenerator(state_dict, arch, fuse_final=fuse_final, fuse_blur=fuse_blur,
                                                                                             precision=precision))
             self._owns_weights = False
@@ -70,6 +97,7 @@ class GeneratorRuntime:
             self.gen = generator or DeoldifyGenerator(state_dict, arch, fuse_final=fuse_final, fuse_blur=fuse_blur, precision=precision)
             self.weights = nat.Weights(ctx, self.gen.blob)
             self._owns_weights = True
+        assert self.gen.precise == (precision == "precise"), "packed model and requested precision differ"
         self.nets = {}
 
     def net(self, S, max_batch=1, low_latency=False):
@@ -101,8 +129,8 @@ class ModelImageRender:
 
     def __init__(self, package_dir=None, modelname="video", render_factor=24, video_weight=0, device_index=0,
                  state_dicts=None, max_batch=1, worker=0, coalesce=0, precision=None, low_latency=None):
-        """`precision`: "fast" (default: fp16 activations and MFMA operands, fp32 accumulation: CIEDE2000 against the reference's fp32 path small
-        in the mean but p99 1.2 - 2.3 on the final image) or "precise" (fp32-class arithmetic like the reference,
+        """`precision`: "fast" (opt-in speed mode: fp16 activations and MFMA operands, fp32 accumulation: CIEDE2000 against the reference's fp32 path small
+        in the mean but p99 1.2 - 2.3 on the final image) or "precise" (the default: fp32-class arithmetic like the reference,
         deoldify/filters.py:45-68: hi / lo fp16 pairs on the same MFMA kernels, 3x the matrix work); None reads HAVC_PRECISION, then the package default "precise" (precision.py).
         `low_latency` (None reads HAVC_LOW_LATENCY, default off): a render that colours ONE frame per call (max_batch <= 2: the reference's call
         shape, vsslib/vsmodels.py:219-230) builds its nets with split-K convs -- a single frame gives most layers 5 - 40 tiles for 256 CUs; bytes
@@ -137,22 +165,14 @@ class ModelImageRender:
                 return GeneratorRuntime(self.ctx, sd, arch, share_key=("sd", id(sd)), precision=self._precision)
         else:
             path = os.path.join(str(self.package_dir), "models", name + ".pth")      # Learner.load path
-            packed = os.path.splitext(path)[0] + ".havc"                             # tools/convert_weights.py output, if newer
-            if self._precision != "fast":                                            # the packed files hold the fast layout: precise packs from the .pth
-                if not os.path.isfile(path) or os.path.getsize(path) == 0:
-                    raise FileNotFoundError(f"DeOldify weights not found: {path}")
-                return GeneratorRuntime(self.ctx, _load_pth(path), arch, share_key=("file", path, os.path.getmtime(path)), precision=self._precision)
-            if os.path.isfile(packed) and (not os.path.isfile(path) or os.path.getmtime(packed) >= os.path.getmtime(path)):
-                key = ("file", packed, os.path.getmtime(packed))
-                if (self.ctx.device_id, arch, True, True) + key in _weights_cache:
-                    return GeneratorRuntime(self.ctx, None, arch, share_key=key)
-                return GeneratorRuntime(self.ctx, None, arch, generator=DeoldifyGenerator.load(packed), share_key=key)
-            if not os.path.isfile(path) or os.path.getsize(path) == 0:
-                raise FileNotFoundError(f"DeOldify weights not found: {path}")
-            key = ("file", path, os.path.getmtime(path))
-            if (self.ctx.device_id, arch, True, True) + key in _weights_cache:
-                return GeneratorRuntime(self.ctx, None, arch, share_key=key)
-            return GeneratorRuntime(self.ctx, _load_pth(path), arch, share_key=key)
+            packed = os.path.splitext(path)[0] + ".havc"                             # tools/convert_weights.py output, if newer and of this precision
+            kind, file = choose_weight_file(path, packed, self._precision)
+            key = ("file", file, os.path.getmtime(file))
+            if (self.ctx.device_id,) + _share_key(arch, True, True, key, self._precision) in _weights_cache:
+                return GeneratorRuntime(self.ctx, None, arch, share_key=key, precision=self._precision)
+            if kind == "havc":
+                return GeneratorRuntime(self.ctx, None, arch, generator=DeoldifyGenerator.load(file), share_key=key, precision=self._precision)
+            return GeneratorRuntime(self.ctx, _load_pth(file), arch, share_key=key, precision=self._precision)
         return GeneratorRuntime(self.ctx, sd, arch, precision=self._precision)
 
     # -- raw batched entry (frames already S x S, uint8 [n,S,S,3]) ------------------------------
