@@ -428,6 +428,27 @@ typedef struct havc_stab_stage {
 /* img -> out through stages[0 .. n_stages - 1], n_stages 0..3 (0: out = img).  width x height pixels: a stack of frames is one tall image.  Host or
  * device pointers like every filter here; out may be img.  A kind, merge_mode, has_adjust or n_ranges outside the values above: HAVC_E_INVALID, nothing runs. */
 int havc_stabilizer_chain(havc_ctx* ctx, const uint8_t* img, uint8_t* out, int width, int height, const havc_stab_stage* stages, int n_stages);
+/* HAVC_clip_slice / HAVC_clip_reconstruct (vsdeoldify/__init__.py:2886-2945 -> vsslib/vstiles4.py): the tiling of the Placebo (4 tiles, 2 x 2) and VerySlow
+ * (2 tiles, side by side) presets.  A clip [n_frames][height][width][3] and its tile clips [n_frames][base_h + overlap_y][base_w + overlap_x][3], in the
+ * order tl, tr, bl, br (2 tiles: tl, tr; then base_h = height and overlap_y = 0).  The tile at (column c, row r) of the grid starts at
+ * (c * (base_w - overlap_x), r * (base_h - overlap_y)) of the clip padded with black on the right and bottom. */
+typedef struct havc_tile_geom {
+    int width, height;        /* of the clip; width <= 2 * base_w, height <= 2 * base_h */
+    int n_frames;
+    int n_tiles;              /* 2 or 4 */
+    int base_w, base_h;       /* HAVC_clip_slice: (width + 1) / 2, (height + 1) / 2 (2 tiles: height) */
+    int overlap_x, overlap_y; /* 0 <= overlap < base */
+    int mask_val;             /* reconstruct: int(round(blend_weight * 255)), 0..255; 0 = the linear ramp min(255, floor((x - start) * 255 / overlap + 0.5)) */
+    int recover_luma;         /* reconstruct: != 0 = luma of clip_orig, chroma of the blend (the body of havc_chroma_post_process) */
+} havc_tile_geom;
+/* clip -> the n_tiles tile clips in ONE launch, black padding included.  Host or device pointers, each on its own; with device pointers only the
+ * call just enqueues.  A geometry outside the limits above: HAVC_E_INVALID, nothing runs. */
+int havc_tile_slice(havc_ctx* ctx, const uint8_t* clip, uint8_t* const* tiles, const havc_tile_geom* geom);
+/* the tile clips (+ clip_orig when recover_luma) -> out [n_frames][height][width][3] in ONE launch: row blend (tl, tr) and (bl, br), column blend of the
+ * two results -- each rounded to u8: out = (a * (255 - m) + b * m + 127) / 255, the stand-in of std.MaskedMerge -- crop, optional luma re-attach.
+ * The mask of a position x is 0 below start = base - overlap (linear ramp: up to and including start), 255 from end = base + overlap, and mask_val or
+ * the ramp between; overlap 0 = plain stacking.  out must be none of the inputs.  clip_orig may be NULL when recover_luma == 0. */
+int havc_tile_reconstruct(havc_ctx* ctx, const uint8_t* const* tiles, const uint8_t* clip_orig, uint8_t* out, const havc_tile_geom* geom);
 /* the per-pixel half of luma_adjusted_levels (vsslib/imfilters.py:335-372): cv2 RGB->YUV, Y' = lut[Y], YUV->RGB.  The caller
  * derives the 256-entry table from havc_image_luma exactly like the reference (vsdeoldify_amd/imfilters.py). */
 int havc_luma_lut(havc_ctx* ctx, const uint8_t* img, const uint8_t* lut256, uint8_t* out, int width, int height);

@@ -19,7 +19,8 @@ def __getattr__(name):
     if name == "DDColorRender":
         from .ddcolor import DDColorRender
         return DDColorRender
-    if name in ("HAVC_colorizer", "HAVC_merge", "HAVC_ddeoldify", "ddeoldify", "HAVC_stabilizer", "HAVCFrameColorizer"):
+    if name in ("HAVC_colorizer", "HAVC_merge", "HAVC_ddeoldify", "ddeoldify", "HAVC_stabilizer", "HAVCFrameColorizer", "HAVC_clip_slice",
+                "HAVC_clip_reconstruct", "ClipTiles", "tiled_preset_params"):
         from . import havc
         return getattr(havc, name)
     if name == "DeviceImage":

@@ -67,6 +67,12 @@ class StabStage(C.Structure):
                 ("hue_ranges", C.c_double * 16)]
 
 
+class TileGeom(C.Structure):
+    """`havc_tile_geom` (include/havc_mi355.h): clip and tile geometry of havc_tile_slice / havc_tile_reconstruct"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int), ("n_tiles", C.c_int), ("base_w", C.c_int), ("base_h", C.c_int),
+                ("overlap_x", C.c_int), ("overlap_y", C.c_int), ("mask_val", C.c_int), ("recover_luma", C.c_int)]
+
+
 class NativeLibraryError(RuntimeError):
     pass
 
@@ -127,6 +133,8 @@ SYMBOLS = [
     ("havc_image_tweak", _I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, C.POINTER(C.c_double), _I]),
     ("havc_image_chroma_tweak", _I, [_P, _P, _P, _I, _I, _D, _D, _I, _I, C.POINTER(C.c_double), _I, _D, _I, _D]),
     ("havc_stabilizer_chain", _I, [_P, _P, _P, _I, _I, _P, _I]),
+    ("havc_tile_slice", _I, [_P, _P, _P, _P]),
+    ("havc_tile_reconstruct", _I, [_P, _P, _P, _P, _P]),
     ("havc_luma_lut", _I, [_P, _P, _P, _P, _I, _I]),
     ("havc_restore_color_gradient", _I, [_P, _P, _P, _P, _I, _I, _D, _I, _D, _D, _I, _I]),
     ("havc_colorize_clip", _I, [_P, _P, _P, _F, _P, _P, _I, _I, _I]),

@@ -9,24 +9,6 @@ static inline int grid_for(int64_t work) {
     return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
 
-// ---- OpenCV RGB2YUV / YUV2RGB, 8-bit (color_yuv.simd.hpp RGB2YCrCb_i / YCrCb2RGB_i, isCrCb=false) ----
-__device__ __forceinline__ int descale14(int x) { return (x + (1 << 13)) >> 14; }
-__device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
-__device__ __forceinline__ void rgb2yuv(int r, int g, int b, int& y, int& u, int& v) {
-    y = descale14(r * 4899 + g * 9617 + b * 1868);
-    u = sat8(descale14((b - y) * 8061 + (128 << 14)));
-    v = sat8(descale14((r - y) * 14369 + (128 << 14)));
-    y = sat8(y);
-}
-__device__ __forceinline__ void yuv2rgb(int y, int u, int v, int& r, int& g, int& b) {
-    u -= 128;
-    v -= 128;
-    b = sat8(y + descale14(u * 33292));
-    g = sat8(y + descale14(u * -6472 + v * -9519));
-    r = sat8(y + descale14(v * 18678));
-}
-
 // ---- PIL Image.blend(a, b, w): (UINT8)((int)a + w * ((int)b - (int)a)) in float32 with the product
 // ROUNDED before the add (Pillow's x86-64 build has no FMA).  HIP's __fmul_rn/__fadd_rn are plain operators
 // and hipcc contracts a + w*d into v_fma_f32 by default, so contraction is switched off explicitly here
@@ -84,10 +66,8 @@ int launch_rgb8_to_planar(const uint8_t* rgb, uint8_t* planes, int64_t npix, hip
 __global__ void yuv_merge_kernel(const uint8_t* __restrict__ color, const uint8_t* __restrict__ orig,
                                  uint8_t* __restrict__ out, int64_t npix) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
-        int y, u, v, y2, u2, v2, r, g, b;
-        rgb2yuv(color[i * 3], color[i * 3 + 1], color[i * 3 + 2], y, u, v);
-        rgb2yuv(orig[i * 3], orig[i * 3 + 1], orig[i * 3 + 2], y2, u2, v2);
-        yuv2rgb(y2, u, v, r, g, b);
+        int r, g, b;
+        yuv_merge_pixel(color[i * 3], color[i * 3 + 1], color[i * 3 + 2], orig[i * 3], orig[i * 3 + 1], orig[i * 3 + 2], r, g, b);
         out[i * 3] = (uint8_t)r; out[i * 3 + 1] = (uint8_t)g; out[i * 3 + 2] = (uint8_t)b;
     }
 }

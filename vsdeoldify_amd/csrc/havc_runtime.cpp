@@ -987,7 +987,7 @@ static void preload_device_locked(int dev) {
     static uint64_t done = 0;                              // guarded by g_setup_mu
     if (done & (1ull << (dev & 63))) return;
     preload_conv_pipe(); preload_conv_igemm(); preload_elementwise(); preload_zhang(); preload_attention(); preload_colorfilters();
-    preload_tweaks(); preload_stabilizer(); preload_ddcolor(); preload_colormnet(); preload_colormnet_net(); preload_precise(); preload_precise2();
+    preload_tweaks(); preload_stabilizer(); preload_tiles(); preload_ddcolor(); preload_colormnet(); preload_colormnet_net(); preload_precise(); preload_precise2();
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(scratch_warm_kernel));
     (void)hipGetLastError();
@@ -1978,6 +1978,91 @@ int havc_stabilizer_chain(havc_ctx* c, const uint8_t* img, uint8_t* out, int wid
     return run_filter(c, img, nullptr, out, nb, "stabilizer_chain", [&](const uint8_t* da, const uint8_t*, uint8_t* dout) {
         if (a.n == 0) return da == dout ? 0 : (int)hipMemcpyAsync(dout, da, nb, hipMemcpyDeviceToDevice, c->stream);
         return launch_stabilizer_chain(da, dout, (int64_t)width * height, a, c->stream); });
+}
+
+// ---- HAVC_clip_slice / HAVC_clip_reconstruct (tiles.hip) ----
+// what keeps every read and write of the two kernels inside its buffer: the tiles cover the clip, the overlaps are smaller than the base tile
+static const char* tile_geom_error(const havc_tile_geom* g) {
+    if (!g || g->width <= 0 || g->height <= 0 || g->n_frames <= 0) return "bad args";
+    if (g->n_tiles != 2 && g->n_tiles != 4) return "n_tiles must be 2 or 4";
+    if (g->base_w <= 0 || g->base_h <= 0 || g->width > 2 * g->base_w) return "the tiles do not cover the clip's width";
+    if (g->n_tiles == 4 ? g->height > 2 * g->base_h : (g->height != g->base_h || g->overlap_y != 0))
+        return "the tiles do not cover the clip's height (2 tiles: base_h = height, overlap_y = 0)";
+    if (g->overlap_x < 0 || g->overlap_y < 0 || g->overlap_x >= g->base_w || (g->n_tiles == 4 && g->overlap_y >= g->base_h))
+        return "an overlap must be >= 0 and smaller than the base tile";
+    if (g->mask_val < 0 || g->mask_val > 255) return "mask_val must be 0..255";
+    return nullptr;
+}
+static TileArgs tile_args(const havc_tile_geom* g) {
+    TileArgs a{};
+    a.w = g->width; a.h = g->height; a.n = g->n_frames; a.n_tiles = g->n_tiles;
+    a.base_w = g->base_w; a.base_h = g->base_h; a.ox = g->overlap_x; a.oy = g->overlap_y; a.mask_val = g->mask_val;
+    return a;
+}
+static size_t tile_stage_bytes(size_t n) { return (n + 255) & ~(size_t)255; }
+
+int havc_tile_slice(havc_ctx* c, const uint8_t* clip, uint8_t* const* tiles, const havc_tile_geom* g) {
+    if (!c || !clip || !tiles) return fail(c, HAVC_E_INVALID, "tile_slice: bad args");
+    if (const char* why = tile_geom_error(g)) return fail(c, HAVC_E_INVALID, (std::string("tile_slice: ") + why).c_str());
+    for (int t = 0; t < g->n_tiles; ++t) if (!tiles[t]) return fail(c, HAVC_E_INVALID, "tile_slice: NULL tile");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    TileArgs a = tile_args(g);
+    const size_t cb = (size_t)a.n * a.h * a.w * 3, tb = (size_t)a.n * (a.base_h + a.oy) * (a.base_w + a.ox) * 3;
+    int rc, n_host = 0;
+    bool host[4] = {false, false, false, false};
+    for (int t = 0; t < a.n_tiles; ++t) n_host += (host[t] = !is_device_ptr(tiles[t]));
+    const uint8_t* d_clip;
+    if ((rc = stage_in(c, 0, clip, cb, &d_clip)) || (n_host && (rc = ensure_scratch(c, 2, tile_stage_bytes(tb) * n_host)))) return rc;
+    for (int t = 0, k = 0; t < a.n_tiles; ++t) a.tile[t] = host[t] ? (uint8_t*)c->scratch[2] + tile_stage_bytes(tb) * k++ : tiles[t];
+    const int e = launch_tile_slice(d_clip, a, c->stream);
+    c->stats.launches++;
+    if (e) return hip_fail(c, (hipError_t)e, "tile_slice");
+    for (int t = 0; t < a.n_tiles; ++t)
+        if (host[t]) HIP_TRY(c, hipMemcpyAsync(tiles[t], a.tile[t], tb, hipMemcpyDeviceToHost, c->stream));
+    if (n_host) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HAVC_OK;
+}
+
+int havc_tile_reconstruct(havc_ctx* c, const uint8_t* const* tiles, const uint8_t* clip_orig, uint8_t* out, const havc_tile_geom* g) {
+    if (!c || !tiles || !out) return fail(c, HAVC_E_INVALID, "tile_reconstruct: bad args");
+    if (const char* why = tile_geom_error(g)) return fail(c, HAVC_E_INVALID, (std::string("tile_reconstruct: ") + why).c_str());
+    if (g->recover_luma && !clip_orig) return fail(c, HAVC_E_INVALID, "tile_reconstruct: recover_luma needs clip_orig");
+    for (int t = 0; t < g->n_tiles; ++t)
+        if (!tiles[t] || tiles[t] == out) return fail(c, HAVC_E_INVALID, "tile_reconstruct: NULL tile, or out is a tile");
+    if (g->recover_luma && clip_orig == out) return fail(c, HAVC_E_INVALID, "tile_reconstruct: out must not be clip_orig");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    TileArgs a = tile_args(g);
+    const size_t cb = (size_t)a.n * a.h * a.w * 3, tb = (size_t)a.n * (a.base_h + a.oy) * (a.base_w + a.ox) * 3;
+    const uint8_t* orig = g->recover_luma ? clip_orig : nullptr;
+    // host operands share one staging buffer (slot 0), sized before the first copy into it
+    size_t need = 0;
+    for (int t = 0; t < a.n_tiles; ++t) if (!is_device_ptr(tiles[t])) need += tile_stage_bytes(tb);
+    if (orig && !is_device_ptr(orig)) need += tile_stage_bytes(cb);
+    int rc;
+    uint8_t* dout;
+    bool host_out;
+    if ((need && (rc = ensure_scratch(c, 0, need))) || (rc = stage_out_ptr(c, 2, out, cb, &dout, &host_out))) return rc;
+    size_t at = 0;
+    auto staged = [&](const uint8_t* p, size_t nb, const uint8_t** d) -> int {
+        if (is_device_ptr(p)) { *d = p; return HAVC_OK; }
+        uint8_t* dst = (uint8_t*)c->scratch[0] + at;
+        at += tile_stage_bytes(nb);
+        HIP_TRY(c, hipMemcpyAsync(dst, p, nb, hipMemcpyHostToDevice, c->stream));
+        *d = dst;
+        return HAVC_OK;
+    };
+    for (int t = 0; t < a.n_tiles; ++t) {
+        const uint8_t* d;
+        if ((rc = staged(tiles[t], tb, &d))) return rc;
+        a.tile[t] = const_cast<uint8_t*>(d);
+    }
+    if (orig && (rc = staged(orig, cb, &orig))) return rc;
+    const int e = launch_tile_reconstruct(a, orig, dout, c->stream);
+    c->stats.launches++;
+    if (e) return hip_fail(c, (hipError_t)e, "tile_reconstruct");
+    return stage_out(c, out, dout, cb, host_out);
 }
 
 int havc_luma_lut(havc_ctx* c, const uint8_t* img, const uint8_t* lut256, uint8_t* out, int width, int height) {

@@ -169,6 +169,17 @@ struct StabStage {
 };
 struct StabChainArgs { int n; StabStage st[HAVC_MAX_STAB_STAGES]; };
 int launch_stabilizer_chain(const uint8_t* img, uint8_t* out, int64_t npix, const StabChainArgs& a, hipStream_t s);
+// tiles.hip: HAVC_clip_slice / HAVC_clip_reconstruct (vsslib/vstiles4.py).  A clip [n][h][w][3] is cut into 2 (side by side) or 4 (2 x 2) overlapping tile
+// clips [n][th][tw][3], tw = base_w + ox, th = base_h + oy (2 tiles: base_h = h, oy = 0), and blended back.  All pointers are device pointers.
+struct TileArgs {
+    uint8_t* tile[4];             // tl, tr, bl, br (2 tiles: tl, tr)
+    int w, h, n;                  // size and frames of the clip
+    int n_tiles;                  // 2 or 4
+    int base_w, base_h, ox, oy;
+    int mask_val;                 // reconstruct: 0 = linear ramp over the overlap, 1..255 = constant weight of the right / bottom tile
+};
+int launch_tile_slice(const uint8_t* clip, const TileArgs& a, hipStream_t s);
+int launch_tile_reconstruct(const TileArgs& a, const uint8_t* orig, uint8_t* out, hipStream_t s);      // orig != null: luma of orig, chroma of the blend
 int launch_restore_color_gradient(const uint8_t* color, const uint8_t* gray, uint8_t* out, int64_t npix, double sat, int tht, double alpha,
                                   double weight, int algo, int return_mask, hipStream_t s);
 // separable polyphase resample of interleaved u8 RGB (tap tables from the host; Spline64 = harness stand-in
@@ -211,6 +222,7 @@ void preload_attention();
 void preload_colorfilters();
 void preload_tweaks();
 void preload_stabilizer();
+void preload_tiles();
 void preload_ddcolor();
 void preload_colormnet();
 void preload_colormnet_net();

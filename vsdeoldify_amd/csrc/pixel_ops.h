@@ -1,5 +1,5 @@
 // Per-pixel bodies of the u8 RGB tweak / luma-merge filters, shared by their stand-alone kernels (tweaks.hip, colorfilters.hip) and by the fused
-// HAVC_stabilizer chain (stabilizer.hip): ONE statement of the arithmetic, so that the fused launch and the chain of single launches give the same bytes.
+// HAVC_stabilizer chain (stabilizer.hip) and the tile reconstruct (tiles.hip): ONE statement of the arithmetic, so that the fused launch and the chain of single launches give the same bytes.
 // Arithmetic restates Pillow's C (libImaging Convert.c / Blend.c: float locals, double intermediates, truncating casts), OpenCV's 8-bit HSV integer
 // path and numpy's float64 merges; see oracle/tweaks.py, oracle/cvcolor.py.  Every translation unit that includes this file is built with
 // -ffp-contract=off: Pillow's / numpy's products are rounded before the add.
@@ -7,6 +7,31 @@
 #include "kernels.h"
 
 __device__ __forceinline__ int clip8i(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// ---- OpenCV RGB2YUV / YUV2RGB, 8-bit (color_yuv.simd.hpp RGB2YCrCb_i / YCrCb2RGB_i, isCrCb=false) ----
+__device__ __forceinline__ int descale14(int x) { return (x + (1 << 13)) >> 14; }
+__device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+__device__ __forceinline__ void rgb2yuv(int r, int g, int b, int& y, int& u, int& v) {
+    y = descale14(r * 4899 + g * 9617 + b * 1868);
+    u = sat8(descale14((b - y) * 8061 + (128 << 14)));
+    v = sat8(descale14((r - y) * 14369 + (128 << 14)));
+    y = sat8(y);
+}
+__device__ __forceinline__ void yuv2rgb(int y, int u, int v, int& r, int& g, int& b) {
+    u -= 128;
+    v -= 128;
+    b = sat8(y + descale14(u * 33292));
+    g = sat8(y + descale14(u * -6472 + v * -9519));
+    r = sat8(y + descale14(v * 18678));
+}
+// chroma_post_process / vs_recover_clip_luma (imfilters.py:312-321, vsfilters.py:863-899), one pixel: Y of the original, U and V of the colour pixel
+__device__ __forceinline__ void yuv_merge_pixel(int cr, int cg, int cb, int or_, int og, int ob, int& r, int& g, int& b) {
+    int y, u, v, y2, u2, v2;
+    rgb2yuv(cr, cg, cb, y, u, v);
+    rgb2yuv(or_, og, ob, y2, u2, v2);
+    yuv2rgb(y2, u, v, r, g, b);
+}
 
 // ---- Pillow rgb2hsv_row / hsv2rgb (Convert.c, "following colorsys.py") ----
 __device__ __forceinline__ void pil_rgb2hsv(int r, int g, int b, int& uh, int& us, int& uv) {

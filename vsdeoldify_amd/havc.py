@@ -2,7 +2,7 @@
 
     HAVC_colorizer   vsdeoldify/__init__.py:2290-2523     HAVC_merge       vsdeoldify/__init__.py:2536-2675
     HAVC_ddeoldify   vsdeoldify/__init__.py:3612-3628     ddeoldify        vsdeoldify/__init__.py:3642-3653
-    HAVC_stabilizer  vsdeoldify/__init__.py:2748-2873
+    HAVC_stabilizer  vsdeoldify/__init__.py:2748-2873     HAVC_clip_slice / HAVC_clip_reconstruct (+ ClipTiles)  vsdeoldify/__init__.py:2886-2945
 
 Same names, argument lists, defaults, parameter normalisation, frame-size rule, model routing, combine dispatch
 (vsslib/mcomb.py:125-192) and error texts; a "clip" is a uint8 array [n, h, w, 3] (or one frame [h, w, 3], or a
@@ -13,12 +13,28 @@ What only VapourSynth can do stays there and is REFUSED here instead of being ap
 sat / hue other than 1 / 0, `luma_mask_sat` < 1), the temporal half of HAVC_stabilizer (`stab=True`), scene detection (`sc_threshold` > 0, `sc_min_freq` > 0), the parts of the DDColor
 pre-tweaks that are VapourSynth filters (`ddtweak`: bright / cont / gamma through vs_tweak, rgb_denoise, retinex), non-RGB24 formats.
 Computed here: the hue adjustment vs_sc_ddcolor applies to every DDColor frame (default "300:360|0.8,0.1") and the luma-constrained
-pre-tweak with its luma recovery (HAVCFrameColorizer._read_ddtweak).  zimg's Spline64 is replaced by the library's own Spline64 (outside the parity
-contract).
+pre-tweak with its luma recovery (HAVCFrameColorizer._read_ddtweak).  What stands in for VapourSynth native code (outside the parity
+contract; none of it can be executed where the fixtures are made, so its integer rounding is unpinned):
+  * zimg's `resize.Spline64` -> the library's own Spline64;
+  * `std.MaskedMerge` under an `akarin.Expr` position mask (HAVC_clip_reconstruct's row and column blends, vsslib/vstiles4.py:281-349) ->
+    out = (a * (255 - m) + b * m + 127) // 255 per channel, rounded to uint8 after each of the two blends; m = 0 gives a and m = 255 gives b exactly;
+  * `vsresize.resize_to_chroma` (HAVC_clip_reconstruct(chroma_resize=True), vsslib/vsresize.py:101-127: a zimg YUV420P8 round trip, BT.709) -> the
+    luma re-attach the rest of this file uses, vs_recover_clip_luma = chroma_post_process (cv2 BT.601 YUV, no chroma subsampling), with clip_orig as
+    the luma source.
+HAVC_clip_slice pads where the reference's std.CropAbs would leave the padded clip by one pixel (an odd width / height with overlap 0: VapourSynth
+raises there); every other geometry CropAbs refuses -- an overlap >= the base tile, a negative overlap -- is refused with HAVCError.
+
+The Placebo / VerySlow presets of HAVC_main (__init__.py:760-767, 862-870) on a clip, host or device:
+
+    ox, oy, rf = tiled_preset_params(width, height, slices)                          # slices: 4 = Placebo, 2 = VerySlow
+    clips = HAVC_clip_slice(clip, slices=slices, overlap_x=ox, overlap_y=oy)
+    for i in range(slices): clips.tiles[i] = HAVC_colorizer(clips.tiles[i], deoldify_p=(0, rf, 1.0, 0.0), ddcolor_p=(1, rf, 1.0, 0.0, True), ...)
+    out = HAVC_clip_reconstruct(clips, blend_weight=0, chroma_resize=True)
 
     out = HAVC_colorizer(clip, method=2, mweight=0.4, torch_dir=..., ...)          # clip: uint8 [n, 1080, 1920, 3]
     col = HAVCFrameColorizer(method=2, mweight=0.4, package_dir=...); out = col.colorize(frame)
 """
+import dataclasses
 import math
 import os
 
@@ -500,4 +516,125 @@ def HAVC_stabilizer(clip, dark=False, dark_p=(0.2, 0.8), smooth=False, smooth_p=
     out = _clip_chroma_resize(clip, col, device_index)                                            # __init__.py:2868-2869: even when every filter is off
     if single:
         return out.reshaped(out.shape[1:]) if is_device(out) else out[0]
+    return out
+
+
+# ---- HAVC_clip_slice / HAVC_clip_reconstruct (vsdeoldify/__init__.py:2886-2945, vsslib/vstiles4.py) ----------------------------------------------------
+@dataclasses.dataclass
+class ClipTiles:
+    """vstiles4.py:28-44.  `tiles` is a plain list: the caller replaces tiles[i] by the colorized tile (__init__.py:865)."""
+    clip_orig: object              # original clip (ndarray, DeviceImage or None)
+    tiles: list                    # [tl, tr, bl, br] or [tl, tr] -- each (base_tile_h + overlap_y) x (base_tile_w + overlap_x)
+    base_tile_w: int               # base tile size (without the overlap)
+    base_tile_h: int
+    overlap_x: int                 # actual overlap in pixels
+    overlap_y: int
+
+
+def tiled_preset_params(width, height, slices):
+    """(overlap_x, overlap_y, render_factor) of the Placebo (slices = 4) / VerySlow (slices = 2) presets, __init__.py:761-764: 20 % of half the clip,
+    between 64 and 192 / 108 pixels, even; the render factor covers a tile's width.  HAVC_clip_slice ignores overlap_y for 2 tiles, as there."""
+    overlap_x = (round(max(min((0.5 * width) * 0.2, 192), 64), 0) // 2) * 2
+    overlap_y = (round(max(min((0.5 * height) * 0.2, 108), 64), 0) // 2) * 2
+    render_factor = min(max(math.trunc((0.5 * width + overlap_x) / 16), 22), 32)
+    return int(overlap_x), int(overlap_y), int(render_factor)
+
+
+def _tile_geometry(w, h, slices, overlap_x, overlap_y):
+    """vstiles4.py:72-83 / :132-141 -> (n_tiles, base_tile_w, base_tile_h, overlap_x, overlap_y); what std.CropAbs would refuse is refused here"""
+    base_w = (w + 1) // 2
+    overlap_x = int((overlap_x // 2) * 2)
+    if slices == 4:
+        n_tiles, base_h, overlap_y = 4, (h + 1) // 2, int((overlap_y // 2) * 2)
+    else:                                                                                        # the reference's `else`: any other value = 2 tiles
+        n_tiles, base_h, overlap_y = 2, h, 0
+    if overlap_x < 0 or overlap_x >= base_w:
+        raise HAVCError(f"HAVC_clip_slice: overlap_x = {overlap_x} must be >= 0 and smaller than the base tile width {base_w}")
+    if overlap_y < 0 or (n_tiles == 4 and overlap_y >= base_h):
+        raise HAVCError(f"HAVC_clip_slice: overlap_y = {overlap_y} must be >= 0 and smaller than the base tile height {base_h}")
+    return n_tiles, base_w, base_h, overlap_x, overlap_y
+
+
+def _tile_ctx(operands):
+    for x in operands:
+        if is_device(x):
+            return x.ctx, True
+    return get_context(0), False
+
+
+def _tile_ptrs(tiles):
+    import ctypes as C
+    from .device import operand_ptr
+    return (C.c_void_p * 4)(*[operand_ptr(t) for t in tiles])
+
+
+def HAVC_clip_slice(clip, slices=2, overlap_x=32, overlap_y=32):
+    """vsdeoldify/__init__.py:2886-2911: the clip cut into 4 (slices == 4: a 2 x 2 grid) or 2 (anything else: side by side) overlapping tiles; the clip is
+    padded with black on the right / bottom by the overlaps (rounded down to even) first.  One launch writes every tile (havc_tile_slice).  ndarray in ->
+    ndarray tiles; DeviceImage in -> DeviceImage tiles (nothing leaves HBM, the call only enqueues)."""
+    if clip is None or not (is_device(clip) or isinstance(clip, np.ndarray)):
+        raise HAVCError("HAVC_clip_slice: this is not a clip")
+    orig = clip
+    clip, single = _as_clip(clip)
+    n, h, w, _ = clip.shape
+    n_tiles, base_w, base_h, ox, oy = _tile_geometry(w, h, slices, overlap_x, overlap_y)
+    ctx, dev = _tile_ctx([clip])
+    shape = (n, base_h + oy, base_w + ox, 3)
+    tiles = [DeviceImage(ctx, shape) if dev else np.empty(shape, np.uint8) for _ in range(n_tiles)]
+    geom = nat.TileGeom(w, h, n, n_tiles, base_w, base_h, ox, oy, 0, 0)
+    from .device import operand_ptr
+    import ctypes as C
+    nat.check(ctx.lib.havc_tile_slice(ctx.h, operand_ptr(clip), _tile_ptrs(tiles), C.byref(geom)), ctx.h)
+    if single:
+        tiles = [t.reshaped(t.shape[1:]) if dev else t[0] for t in tiles]
+    return ClipTiles(clip_orig=orig, tiles=tiles, base_tile_w=base_w, base_tile_h=base_h, overlap_x=ox, overlap_y=oy)
+
+
+def HAVC_clip_reconstruct(clip_tiles, blend_weight=0.5, chroma_resize=False):
+    """vsdeoldify/__init__.py:2922-2945: the tiles blended back into one clip of clip_orig's size (vstiles4.py:161-348) -- rows (tl, tr) and (bl, br), then the
+    two results as columns, each blend rounded to uint8; blend_weight 0 (mask value int(round(blend_weight * 255)) == 0) = a linear ramp over the overlap,
+    otherwise that constant weight for the right / bottom tile; chroma_resize = the luma of clip_orig under the blend's chroma.  One launch
+    (havc_tile_reconstruct).  Host and device operands may be mixed: any DeviceImage -> a DeviceImage comes back and the call only enqueues."""
+    tiles = list(clip_tiles.tiles)
+    if len(tiles) not in (2, 4):
+        raise HAVCError(f"HAVC_clip_reconstruct: 2 or 4 tiles expected, got {len(tiles)}")
+    for t in tiles:
+        if t is None or not (is_device(t) or isinstance(t, np.ndarray)):
+            raise HAVCError("HAVC_clip_reconstruct: this is not a clip: tiles")
+    orig = clip_tiles.clip_orig
+    if orig is None and chroma_resize:
+        raise HAVCError("HAVC_clip_reconstruct: chroma_resize=True needs clip_orig (the luma source)")
+    if orig is not None and not (is_device(orig) or isinstance(orig, np.ndarray)):
+        raise HAVCError("HAVC_clip_reconstruct: this is not a clip: clip_orig")
+    mask_val = int(round(blend_weight * 255))                                                     # vstiles4.py:284
+    if not 0 <= mask_val <= 255:
+        raise HAVCError("HAVC_clip_reconstruct: blend_weight must be between 0 and 1")
+    base_w, base_h, ox, oy = (int(v) for v in (clip_tiles.base_tile_w, clip_tiles.base_tile_h, clip_tiles.overlap_x, clip_tiles.overlap_y))
+    ox, oy = max(ox, 0), max(oy, 0)                                                               # overlap <= 0: plain stacking (vstiles4.py:316-317, 337-338)
+    single = tiles[0].ndim == 3
+    tiles = [_as_clip(t)[0] for t in tiles]
+    n = tiles[0].shape[0]
+    if len(tiles) == 2:
+        oy = 0
+    full_w, full_h = 2 * base_w, (2 * base_h if len(tiles) == 4 else base_h)
+    if base_w <= 0 or base_h <= 0 or ox >= base_w or (len(tiles) == 4 and oy >= base_h):
+        raise HAVCError("HAVC_clip_reconstruct: an overlap must be smaller than the base tile")
+    for t in tiles:
+        if tuple(t.shape) != (n, base_h + oy, base_w + ox, 3):
+            raise HAVCError(f"HAVC_clip_reconstruct: a tile of shape {tuple(t.shape)} does not match base tile + overlap = {(n, base_h + oy, base_w + ox, 3)}")
+    if orig is not None:
+        orig, _ = _as_clip(orig)
+        if orig.shape[0] != n or orig.shape[2] > full_w or orig.shape[1] > full_h or (len(tiles) == 2 and orig.shape[1] != full_h):
+            raise HAVCError(f"HAVC_clip_reconstruct: clip_orig of shape {tuple(orig.shape)} is not covered by the tiles ({n} frames of {full_h} x {full_w})")
+        h, w = orig.shape[1:3]
+    else:
+        h, w = full_h, full_w
+    ctx, dev = _tile_ctx(tiles + [orig])
+    out = DeviceImage(ctx, (n, h, w, 3)) if dev else np.empty((n, h, w, 3), np.uint8)
+    geom = nat.TileGeom(w, h, n, len(tiles), base_w, base_h, ox, oy, mask_val, 1 if chroma_resize else 0)
+    from .device import operand_ptr
+    import ctypes as C
+    nat.check(ctx.lib.havc_tile_reconstruct(ctx.h, _tile_ptrs(tiles), operand_ptr(orig) if chroma_resize else None, operand_ptr(out), C.byref(geom)), ctx.h)
+    if single:
+        return out.reshaped(out.shape[1:]) if dev else out[0]
     return out
