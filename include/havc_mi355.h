@@ -449,6 +449,34 @@ int havc_tile_slice(havc_ctx* ctx, const uint8_t* clip, uint8_t* const* tiles, c
  * The mask of a position x is 0 below start = base - overlap (linear ramp: up to and including start), 255 from end = base + overlap, and mask_val or
  * the ramp between; overlap 0 = plain stacking.  out must be none of the inputs.  clip_orig may be NULL when recover_luma == 0. */
 int havc_tile_reconstruct(havc_ctx* ctx, const uint8_t* const* tiles, const uint8_t* clip_orig, uint8_t* out, const havc_tile_geom* geom);
+/* HAVC_SceneDetect's per-frame statistics (vsslib/vsscdect.py:200-238, 281-298): what the reference's detector reads of a frame -- the mean of a small gray
+ * plane and std.PlaneStats' difference against the frame `offset` frames before -- for a whole clip [n_frames][height][width][3], as exact integers.
+ *   Y = (cr * R + cg * G + cb * B + bias) >> 16   the gray plane: a stand-in of zimg's RGB -> GRAY8 (matrix 709), coefficients from the caller
+ *                                                  (vsdeoldify_amd/scdetect.py: limited range 11966 / 40254 / 4064 / 16.5 * 65536, full range 13933 / 46871 / 4732 / 32768)
+ * normalize != 0 restates vsutils.frame_normalize (vsslib/vsutils.py:304-318): a frame whose own mean(Y) / 255 lies strictly between tht_black and tht_white
+ * has its plane replaced by uint8(255 * ((Y - min) / (max - min))) -- float64: divide, multiply, truncate -- before sum_y and sad are taken; a flat frame
+ * (max == min; NaN in the reference) becomes all zeros.  Without normalize the whole clip is ONE launch; with it two dependent launches, the second
+ * reading the first one's results on the device. */
+typedef struct havc_scene_params {
+    int width, height, n_frames;
+    int offset;                   /* 1..25: frame n is compared with frame max(n - offset, 0) */
+    int cr, cg, cb, bias;         /* >= 0 and (cr + cg + cb) * 255 + bias < 256 << 16 */
+    int normalize;
+    int reserved;
+    double tht_black, tht_white;  /* used with normalize: 0 <= tht_black <= tht_white <= 1 */
+} havc_scene_params;
+typedef struct havc_scene_rec {
+    int64_t sum_y;                /* sum of the frame's gray plane (the normalised plane with normalize) */
+    int64_t sad;                  /* sum of |Y_n - Y_max(n - offset, 0)| over the (normalised) planes; 0 for frame 0 */
+    int64_t sum_raw;              /* sum of the gray plane before normalisation (== sum_y without normalize) */
+    int32_t min_y, max_y;         /* extrema of the gray plane before normalisation */
+} havc_scene_rec;
+/* clip: host or device pointer like every filter here (a device clip is read in place).  out: n_frames records in HOST memory; the call blocks until
+ * they are there -- the records are the only bytes that come back.  Sums are integers: the result is bit-identical from run to run.  Anything outside the
+ * limits above: HAVC_E_INVALID, nothing runs. */
+int havc_scene_stats(havc_ctx* ctx, const uint8_t* clip, const havc_scene_params* params, havc_scene_rec* out);
+/* the normalisation's arithmetic on one value, on the host: k = Y - min, d = max - min -> uint8(255 * (k / d)); d == 0 -> 0.  No context, no GPU. */
+int havc_scene_norm_value(int k, int d);
 /* the per-pixel half of luma_adjusted_levels (vsslib/imfilters.py:335-372): cv2 RGB->YUV, Y' = lut[Y], YUV->RGB.  The caller
  * derives the 256-entry table from havc_image_luma exactly like the reference (vsdeoldify_amd/imfilters.py). */
 int havc_luma_lut(havc_ctx* ctx, const uint8_t* img, const uint8_t* lut256, uint8_t* out, int width, int height);

@@ -73,6 +73,16 @@ class TileGeom(C.Structure):
                 ("overlap_x", C.c_int), ("overlap_y", C.c_int), ("mask_val", C.c_int), ("recover_luma", C.c_int)]
 
 
+class SceneParams(C.Structure):
+    """`havc_scene_params` (include/havc_mi355.h): clip size, offset, luma coefficients and normalisation of havc_scene_stats"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int), ("offset", C.c_int), ("cr", C.c_int), ("cg", C.c_int), ("cb", C.c_int),
+                ("bias", C.c_int), ("normalize", C.c_int), ("reserved", C.c_int), ("tht_black", C.c_double), ("tht_white", C.c_double)]
+
+
+# numpy mirror of `havc_scene_rec`: one record per frame
+SCENE_REC_DTYPE = np.dtype([("sum_y", "<i8"), ("sad", "<i8"), ("sum_raw", "<i8"), ("min_y", "<i4"), ("max_y", "<i4")], align=True)
+
+
 class NativeLibraryError(RuntimeError):
     pass
 
@@ -135,6 +145,8 @@ SYMBOLS = [
     ("havc_stabilizer_chain", _I, [_P, _P, _P, _I, _I, _P, _I]),
     ("havc_tile_slice", _I, [_P, _P, _P, _P]),
     ("havc_tile_reconstruct", _I, [_P, _P, _P, _P, _P]),
+    ("havc_scene_stats", _I, [_P, _P, _P, _P]),
+    ("havc_scene_norm_value", _I, [_I, _I]),
     ("havc_luma_lut", _I, [_P, _P, _P, _P, _I, _I]),
     ("havc_restore_color_gradient", _I, [_P, _P, _P, _P, _I, _I, _D, _I, _D, _D, _I, _I]),
     ("havc_colorize_clip", _I, [_P, _P, _P, _F, _P, _P, _I, _I, _I]),

@@ -290,8 +290,8 @@ class DeepExColorMNet:
     """The data path of HAVC_deepex(ex_model=0) (vsdeoldify/__init__.py:1665-1735) on arrays, without VapourSynth: SmartResizeColorizer
     (vsslib/vsresize.py:271-329: black borders up to the target aspect ratio, Spline64 to the DeepEx size) -> ColorMNetRender per frame, the
     reference frames arriving with the frames a scene detector flagged (colormnet/__init__.py:100-112) -> Spline64 back, borders cropped ->
-    luma of the source (vs_recover_clip_luma).  Scene detection itself, the HAVC-generated reference clip, ref_merge and the dark / smooth /
-    colormap tweaks of the reference frames stay in VapourSynth: pass the reference images.  Spline64 = the library's (zimg is outside the
+    luma of the source (vs_recover_clip_luma).  havc.HAVC_deepex drives it with scene flags (havc.HAVC_SceneDetect), ref_merge and the dark / smooth /
+    colormap tweaks of the reference frames; driven by hand, pass the reference images.  Spline64 = the library's (zimg is outside the
     parity contract)."""
 
     def __init__(self, vid_length, render_speed="medium", enable_resize=False, render_vivid=True, max_memory_frames=0, frame_propagate=False,
@@ -336,14 +336,19 @@ class DeepExColorMNet:
         small, pads = self._squash(frame, ctx)
         return (small if is_device(small) else Image.fromarray(small)), pads
 
-    def colorize_frame(self, frame, ref=None, _small=None, _slot=None, _next_plain=False):
+    def colorize_frame(self, frame, ref=None, _small=None, _slot=None, _next_plain=False, ref_small=None, blend=None):
         """frame: u8 [h, w, 3] (ndarray or DeviceImage); ref: the reference image for THIS frame (same size as the clip) or None.
+        ref_small (HAVC_deepex): the reference image ALREADY at the DeepEx size (squashed by _squash and tweaked by the caller), instead of ref.
+        blend = (image at the DeepEx size, weight) (HAVC_deepex with ref_merge): the coloured small frame is merged with it -- image_weighted_merge,
+        colormnet/__init__.py:99-100 -- before the Spline64 pass back.
         _slot (colorize_frames): a frame of a window-sized low-resolution buffer -- the coloured small frame is written there and RETURNED without the
         Spline64 pass back to the clip size, which the caller then runs once for the whole window.  _next_plain (colorize_frames): the next call is the
         next announced frame and carries no reference image (ColorMNetRender._colorize_frame_fast may start its read early)."""
         from .device import is_device
         from .havc import spline64
         h, w = frame.shape[:2]
+        if ref_small is not None:                                            # a frame that carries a reference, whichever way it arrives: the guard below
+            ref = ref_small                                                  # must see it -- such a frame is read on the network's own stream
         if _small is None and is_device(frame) and frame.complete and ref is None and self.render.first_mask_loaded and frame.ctx is self.render.network.ctx:
             # a resident frame nobody announced: squashed on the look-ahead context, where its key encoder will run -- nothing of this frame's
             # preparation waits for the memory step of the previous one (ColorMNetRender._colorize_frame_fast)
@@ -353,7 +358,7 @@ class DeepExColorMNet:
                 _small = self._small(frame, la_ctx)
                 _small[0].produced_on_lookahead = True
         small, (ph, pw) = _small if _small is not None else self._small(frame)
-        if ref is not None:
+        if ref_small is None and ref is not None:
             rs, _ = self._squash(ref)
             ref = rs if is_device(rs) else np.asarray(rs)
         self.render.set_ref_frame(ref, self.propagate)
@@ -369,6 +374,9 @@ class DeepExColorMNet:
             col = self.render.colorize_frame(self.t, small)
             self.t += 1
         col = col if is_device(col) else np.asarray(col)
+        if blend is not None:
+            from . import imfilters as F
+            col = F.blend_np(self.ctx, col, blend[0], blend[1])
         if ph or pw:                                                         # restore_clip_size: Spline64 to the bordered size, crop, then the luma
             up = spline64(self.ctx, col, w + 2 * pw, h + 2 * ph)
             up = (up.numpy() if is_device(up) else up)[ph:ph + h, pw:pw + w]

@@ -2,6 +2,7 @@
 // Implements include/havc_mi355.h.  No torch, no Python: plain HIP runtime + the kernels in this directory.
 #include "../../include/havc_mi355.h"
 #include "kernels.h"
+#include "scdetect_ops.h"
 #include "build_stamp.h"
 
 #include <algorithm>
@@ -987,7 +988,7 @@ static void preload_device_locked(int dev) {
     static uint64_t done = 0;                              // guarded by g_setup_mu
     if (done & (1ull << (dev & 63))) return;
     preload_conv_pipe(); preload_conv_igemm(); preload_elementwise(); preload_zhang(); preload_attention(); preload_colorfilters();
-    preload_tweaks(); preload_stabilizer(); preload_tiles(); preload_ddcolor(); preload_colormnet(); preload_colormnet_net(); preload_precise(); preload_precise2();
+    preload_tweaks(); preload_stabilizer(); preload_tiles(); preload_scdetect(); preload_ddcolor(); preload_colormnet(); preload_colormnet_net(); preload_precise(); preload_precise2();
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(scratch_warm_kernel));
     (void)hipGetLastError();
@@ -2063,6 +2064,42 @@ int havc_tile_reconstruct(havc_ctx* c, const uint8_t* const* tiles, const uint8_
     c->stats.launches++;
     if (e) return hip_fail(c, (hipError_t)e, "tile_reconstruct");
     return stage_out(c, out, dout, cb, host_out);
+}
+
+// ---- HAVC_SceneDetect's per-frame statistics (scdetect.hip) ----
+static_assert(sizeof(SceneRec) == sizeof(havc_scene_rec) && sizeof(havc_scene_rec) == 32, "havc_scene_rec layout");
+
+int havc_scene_norm_value(int k, int d) { return scene_norm_value(k, d); }
+
+int havc_scene_stats(havc_ctx* c, const uint8_t* clip, const havc_scene_params* p, havc_scene_rec* out) {
+    if (!c || !clip || !p || !out) return fail(c, HAVC_E_INVALID, "scene_stats: bad args");
+    if (p->width <= 0 || p->height <= 0 || p->n_frames <= 0 || (int64_t)p->width * p->height > ((int64_t)1 << 31))
+        return fail(c, HAVC_E_INVALID, "scene_stats: bad clip size (at most 2^31 pixels per frame)");
+    if (p->offset < 1 || p->offset > 25) return fail(c, HAVC_E_INVALID, "scene_stats: offset must be 1..25");
+    if (p->cr < 0 || p->cg < 0 || p->cb < 0 || p->bias < 0 || ((int64_t)p->cr + p->cg + p->cb) * 255 + p->bias >= ((int64_t)256 << 16))
+        return fail(c, HAVC_E_INVALID, "scene_stats: luma coefficients must be >= 0 and keep Y = (cr*R + cg*G + cb*B + bias) >> 16 below 256");
+    if (p->normalize && !(p->tht_black >= 0.0 && p->tht_white <= 1.0 && p->tht_black <= p->tht_white))
+        return fail(c, HAVC_E_INVALID, "scene_stats: normalize needs 0 <= tht_black <= tht_white <= 1");
+    if (is_device_ptr(out)) return fail(c, HAVC_E_INVALID, "scene_stats: the records are downloaded: out must be host memory");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    SceneStatsArgs a{};
+    a.n = p->n_frames; a.h = p->height; a.w = p->width; a.offset = p->offset;
+    a.cr = p->cr; a.cg = p->cg; a.cb = p->cb; a.bias = p->bias;
+    a.normalize = p->normalize != 0; a.tht_black = p->tht_black; a.tht_white = p->tht_white;
+    const size_t cb = (size_t)a.n * a.h * a.w * 3, rb = (size_t)a.n * sizeof(SceneRec);
+    int rc;
+    const uint8_t* d_clip;
+    if ((rc = stage_in(c, 0, clip, cb, &d_clip)) || (rc = ensure_scratch(c, 6, rb))) return rc;
+    SceneRec* d_rec = (SceneRec*)c->scratch[6];
+    HIP_TRY(c, hipMemsetAsync(d_rec, 0, rb, c->stream));
+    const int e = launch_scene_stats(d_clip, d_rec, a, c->stream);
+    c->stats.launches += a.normalize ? 2 : 1;
+    if (e) return hip_fail(c, (hipError_t)e, "scene_stats");
+    HIP_TRY(c, hipMemcpyAsync(out, d_rec, rb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < a.n; ++i) out[i].min_y = 255 - out[i].min_y;       // kept as 255 - min on the device (scdetect.hip)
+    return HAVC_OK;
 }
 
 int havc_luma_lut(havc_ctx* c, const uint8_t* img, const uint8_t* lut256, uint8_t* out, int width, int height) {

@@ -180,6 +180,17 @@ struct TileArgs {
 };
 int launch_tile_slice(const uint8_t* clip, const TileArgs& a, hipStream_t s);
 int launch_tile_reconstruct(const TileArgs& a, const uint8_t* orig, uint8_t* out, hipStream_t s);      // orig != null: luma of orig, chroma of the blend
+// scdetect.hip: per-frame scene statistics of a clip [n][h][w][3] (gray sum, min, max, SAD against the frame `offset` frames before).  SceneRec is the
+// layout of havc_scene_rec (include/havc_mi355.h); on the device min_y holds 255 - min until the runtime has downloaded the records.
+struct SceneRec { long long sum_y, sad, sum_raw; int min_y, max_y; };
+struct SceneStatsArgs {
+    int n, h, w, offset;
+    int cr, cg, cb, bias;         // Y = (cr * R + cg * G + cb * B + bias) >> 16, at most 255 (checked by havc_scene_stats)
+    int normalize;                // frame_normalize between tht_black and tht_white: two dependent launches
+    int blocks_per_frame;         // set by launch_scene_stats
+    double tht_black, tht_white;
+};
+int launch_scene_stats(const uint8_t* clip, SceneRec* rec, SceneStatsArgs a, hipStream_t s);   // rec: n zero-filled device records
 int launch_restore_color_gradient(const uint8_t* color, const uint8_t* gray, uint8_t* out, int64_t npix, double sat, int tht, double alpha,
                                   double weight, int algo, int return_mask, hipStream_t s);
 // separable polyphase resample of interleaved u8 RGB (tap tables from the host; Spline64 = harness stand-in
@@ -223,6 +234,7 @@ void preload_colorfilters();
 void preload_tweaks();
 void preload_stabilizer();
 void preload_tiles();
+void preload_scdetect();
 void preload_ddcolor();
 void preload_colormnet();
 void preload_colormnet_net();

@@ -3,6 +3,8 @@
     HAVC_colorizer   vsdeoldify/__init__.py:2290-2523     HAVC_merge       vsdeoldify/__init__.py:2536-2675
     HAVC_ddeoldify   vsdeoldify/__init__.py:3612-3628     ddeoldify        vsdeoldify/__init__.py:3642-3653
     HAVC_stabilizer  vsdeoldify/__init__.py:2748-2873     HAVC_clip_slice / HAVC_clip_reconstruct (+ ClipTiles)  vsdeoldify/__init__.py:2886-2945
+    HAVC_SceneDetect vsdeoldify/__init__.py:3191-3225     (-> scdetect.SceneInfo: arrays carry no frame props)
+    HAVC_deepex      vsdeoldify/__init__.py:1421-1735     (ex_model 0 = ColorMNet, method 0; `scenes=` is the SceneInfo the reference reads off clip_ref's props)
 
 Same names, argument lists, defaults, parameter normalisation, frame-size rule, model routing, combine dispatch
 (vsslib/mcomb.py:125-192) and error texts; a "clip" is a uint8 array [n, h, w, 3] (or one frame [h, w, 3], or a
@@ -10,7 +12,9 @@ Same names, argument lists, defaults, parameter normalisation, frame-size rule, 
 behind `HAVC_colorizer` (models and nets are built once and reused between calls).
 
 What only VapourSynth can do stays there and is REFUSED here instead of being approximated: `vs_tweak` (deoldify / ddcolor
-sat / hue other than 1 / 0, `luma_mask_sat` < 1), the temporal half of HAVC_stabilizer (`stab=True`), scene detection (`sc_threshold` > 0, `sc_min_freq` > 0), the parts of the DDColor
+sat / hue other than 1 / 0, `luma_mask_sat` < 1), the temporal half of HAVC_stabilizer (`stab=True`), scene detection INSIDE HAVC_colorizer / HAVC_ddeoldify (`sc_threshold` > 0, `sc_min_freq` > 0: the reference-frame
+logic of vs_sc_ddcolor / vs_sc_tweak that hangs off it), the SSIM post-filter of HAVC_SceneDetect (`sc_tht_ssim` in (0, 1), `sc_min_int` > 1: skimage + cv2 histograms), of HAVC_deepex the exemplar models 1-3 (Deep-Exemplar, DeepRemaster: not built), methods 1-6
+(reference frames from a directory or a video), `encode_mode` 2 and `sc_framedir` / `only_ref_frames` (they write files), the parts of the DDColor
 pre-tweaks that are VapourSynth filters (`ddtweak`: bright / cont / gamma through vs_tweak, rgb_denoise, retinex), non-RGB24 formats.
 Computed here: the hue adjustment vs_sc_ddcolor applies to every DDColor frame (default "300:360|0.8,0.1") and the luma-constrained
 pre-tweak with its luma recovery (HAVCFrameColorizer._read_ddtweak).  What stands in for VapourSynth native code (outside the parity
@@ -21,6 +25,11 @@ contract; none of it can be executed where the fixtures are made
   * `vsresize.resize_to_chroma` (HAVC_clip_reconstruct(chroma_resize=True), vsslib/vsresize.py:101-127: a zimg YUV420P8 round trip, BT.709) -> the
     luma re-attach the rest of this file uses, vs_recover_clip_luma = chroma_post_process (cv2 BT.601 YUV, no chroma subsampling), with clip_orig as
     the luma source.
+  * HAVC_SceneDetect (vsdeoldify_amd/scdetect.py has the details): zimg's RGB -> GRAY8 with matrix 709 -> Y = (cr * R + cg * G + cb * B + bias) >> 16, limited
+    range by default (VapourSynth's default for non-RGB output; `luma_range="full"` exists because that assumption cannot be checked here); `resize_min_HW`'s zimg
+    Spline36 on the gray plane -> the library's Spline64 on the RGB clip, at the reference's size; `misc.SCDetect` on the default path (threshold >= 0.10,
+    offset 1) -> prev_n = diff(n - 1, n) > threshold, prev_0 = 1, next_n = prev_(n + 1), next_last = 1.  The custom detector (threshold < 0.10 or offset > 1) and
+    the black / white filter are the reference's Python, restated and pinned by tests/golden/scdetect.npz.
 HAVC_clip_slice pads where the reference's std.CropAbs would leave the padded clip by one pixel (an odd width / height with overlap 0: VapourSynth
 raises there); every other geometry CropAbs refuses -- an overlap >= the base tile, a negative overlap -- is refused with HAVCError.
 
@@ -638,3 +647,178 @@ def HAVC_clip_reconstruct(clip_tiles, blend_weight=0.5, chroma_resize=False):
     if single:
         return out.reshaped(out.shape[1:]) if dev else out[0]
     return out
+
+
+# ---- HAVC_SceneDetect (vsdeoldify/__init__.py:3191-3225 -> vsslib/vsscdect.py) --------------------------------------------------------------------------
+def HAVC_SceneDetect(clip, sc_threshold=0.10, sc_tht_offset=1, sc_tht_ssim=0.0, sc_min_int=1, sc_min_freq=0, sc_normalize=False, sc_tht_white=0.70,
+                     sc_tht_black=0.10, sc_debug=False, *, device_index=0, luma_range="limited"):
+    """vsdeoldify/__init__.py:3191-3225: the scene-change frames of a clip.  The reference sets frame props; arrays carry none, so the props come back as a
+    `scdetect.SceneInfo` (scene_change_prev / scene_change_next / sc_luma / sc_ratio per frame + sc_threshold / sc_frequency).  The per-frame statistics
+    are ONE launch over the clip (havc_scene_stats; two with sc_normalize); a DeviceImage stays in HBM and only the per-frame records come back.  The
+    decision is scdetect.scene_flags, on the host.  sc_debug is accepted and ignored.  luma_range ("limited" / "full") picks the gray conversion's
+    coefficients (module docstring).  The SSIM post-filter is refused before anything is enqueued."""
+    from . import scdetect
+    if clip is None or not (is_device(clip) or isinstance(clip, np.ndarray)):
+        raise HAVCError("HAVC_SceneDetect: this is not a clip")
+    if luma_range not in ("limited", "full"):
+        raise HAVCError("HAVC_SceneDetect: luma_range must be 'limited' or 'full'")
+    branch = scdetect.detect_branch(sc_threshold, sc_min_freq, sc_tht_ssim, sc_min_int, sc_tht_offset)     # raises for the SSIM filter (vsscdect.py:227-233)
+    clip, _ = _as_clip(clip)
+    ctx = None                                                                                   # the early returns touch no pixel and need no context
+    if branch in ("custom", "plugin"):
+        ctx = clip.ctx if is_device(clip) else get_context(device_index)
+    return scdetect.scene_detect(ctx, clip, threshold=sc_threshold, frequency=sc_min_freq, sc_tht_filter=sc_tht_ssim, min_length=sc_min_int,
+                                 tht_white=sc_tht_white, tht_black=sc_tht_black, frame_norm=sc_normalize, tht_offset=sc_tht_offset,
+                                 coeffs=scdetect.LUMA_LIMITED if luma_range == "limited" else scdetect.LUMA_FULL)
+
+
+# ---- HAVC_deepex (vsdeoldify/__init__.py:1421-1735), ex_model 0 = ColorMNet, method 0 = reference frames from clip_ref -------------------------------------
+_REFMERGE_WEIGHT = [0.0, 0.3, 0.4, 0.5, 0.6, 0.7]                                                  # __init__.py:1631
+
+
+def _deepex_checks(clip, clip_ref, method, ref_merge, sc_framedir, only_ref_frames, ex_model, encode_mode, scenes):
+    """the reference's argument checks in its order (__init__.py:1540-1590) as HAVCError, then what this library refuses, each with its reason"""
+    def bad(msg):
+        raise HAVCError(msg)
+    if only_ref_frames and sc_framedir is None:
+        bad("HAVC_deepex: only_ref_frames is enabled but sc_framedir is unset")
+    if sc_framedir is not None and method != 0 and only_ref_frames:
+        bad("HAVC_deepex: only_ref_frames is enabled but method != 0 (HAVC)")
+    if method != 0 and sc_framedir is None:
+        bad("HAVC_deepex: method != 0 but sc_framedir is unset")
+    if method in (3, 4) and clip_ref is not None:
+        bad("HAVC_deepex: method in (3, 4) but clip_ref is set")
+    if method in (0, 1, 2, 5, 6) and clip_ref is None:
+        bad("HAVC_deepex: method in (0, 1, 2, 5, 6) but clip_ref is unset")
+    if clip_ref is not None and not (is_device(clip_ref) or isinstance(clip_ref, np.ndarray)):
+        bad("HAVC_deepex: this is not a clip: clip_ref")
+    if method not in range(7):
+        bad("HAVC_deepex: method must be in range [0-6]")
+    if ref_merge not in range(6):
+        bad("HAVC_deepex: ref_merge must be in range [0-5]")
+    if ref_merge > 0 and (method not in (0, 1, 5) and ex_model != 3):
+        bad("HAVC_deepex: method must be in (0, 1, 5) to be used with ref_merge > 0")
+    if method in (0, 1, 2):
+        # get_sc_props(clip_ref): arrays carry no frame props, `scenes` is what the reference reads off clip_ref; no props = (0, 0) there (vsscdect.py:104-115)
+        sc_threshold, sc_frequency = (scenes.sc_threshold, scenes.sc_frequency) if scenes is not None else (0, 0)
+        if sc_threshold == 0 and sc_frequency == 0:
+            bad("HAVC_deepex: method in (0, 1, 2) but sc_threshold and sc_frequency are not set")
+        if sc_frequency == 1 and only_ref_frames:
+            bad("HAVC_deepex: only_ref_frames is enabled but sc_frequency == 1 or ColorTemp/FrameInterp are set ")
+        if not only_ref_frames and ref_merge > 0 and sc_frequency != 1 and ex_model != 3:
+            bad("HAVC_deepex: method in (0, 1, 2) and ref_merge > 0 but sc_frequency != 1")
+    if method in (0, 1, 2) and ex_model == 2:
+        bad("HAVC_deepex: DeepRemaster cannot be used with methods: 0, 1, 2 (HAVC)")
+    if ex_model in (1, 2, 3):
+        raise NotImplementedError("HAVC_deepex: ex_model 1-3 (Deep-Exemplar, DeepRemaster, Deep-CMnet) are not built: only ColorMNet (ex_model = 0) is, DESIGN.md section 7")
+    if ex_model != 0:
+        bad("HybridAVC: unknown exemplar model id: " + str(ex_model))                             # __init__.py:1724
+    if method != 0:
+        raise NotImplementedError("HAVC_deepex: methods 1-6 take their reference frames from a directory or a video (sc_framedir, HAVC_restore_video): "
+                                  "only method 0 (reference frames from clip_ref) is built")
+    if sc_framedir is not None or only_ref_frames:
+        raise NotImplementedError("HAVC_deepex: sc_framedir / only_ref_frames write the reference frames to files: not in this harness")
+    if encode_mode == 2:
+        raise NotImplementedError("HAVC_deepex: encode_mode = 2 is not built; 0 and 1 both run in process, as DeepExColorMNet does")
+    if encode_mode not in (0, 1):
+        bad("HAVC_deepex: encode_mode must be 0, 1 or 2")
+
+
+def HAVC_deepex(clip=None, clip_ref=None, method=0, render_speed='medium', render_vivid=True, ref_merge=0, sc_framedir=None, ref_norm=False,
+                only_ref_frames=False, dark=False, dark_p=(0.2, 0.8), smooth=False, smooth_p=(0.3, 0.7, 0.9, 0.0, "none"), colormap="none",
+                ref_weight=None, ref_thresh=None, ref_freq=None, ex_model=0, encode_mode=0, max_memory_frames=0, torch_dir=None, *, scenes=None, **harness):
+    """vsdeoldify/__init__.py:1421-1735 with ex_model = 0 (ColorMNet) and method = 0 (reference frames from clip_ref, e.g. HAVC_colorizer's output): every
+    frame `scenes` flags (and frame 0) hands its clip_ref frame to ColorMNet as the new reference, the others are propagated.  `scenes` is the SceneInfo the
+    reference reads off clip_ref's frame props (get_sc_props, CopySCDetect): HAVC_SceneDetect's result for the clip clip_ref was made of.  ref_merge > 0 (with
+    scenes.sc_frequency == 1: every frame has a reference) detects the scenes of `clip` itself (threshold ref_thresh, frequency ref_freq, ref_norm) and merges
+    every frame that is no scene change with its squashed reference frame at weight ref_weight (default [0, .3, .4, .5, .6, .7][ref_merge]).  colormap ->
+    dark -> smooth are applied to the squashed reference frames that are scene changes (vs_sc_*: vsfilters.py:525-636), one launch (havc_stabilizer_chain); a
+    colormap NAME goes through _get_colormap as in HAVC_stabilizer (the reference hands the bare name to image_chroma_tweak, where its parser raises).
+    ndarray in -> ndarray out; a DeviceImage clip (and clip_ref) stays in HBM end to end.  Frames go through DeepExColorMNet.colorize_frame one by one.
+    `harness` = keyword-only extras of this library: state_dict / network (seeded ColorMNet weights or a built ColorMNetNetwork instead of the files under
+    torch_dir), device_index, luma_range (HAVC_SceneDetect's), debug (a dict that receives "ref_small": the squashed, tweaked reference frames by index,
+    "clip_sc": the SceneInfo of clip, "ref_weight")."""
+    if clip is None or not (is_device(clip) or isinstance(clip, np.ndarray)):
+        raise HAVCError("HAVC_deepex: this is not a clip")
+    unknown = set(harness) - {"state_dict", "network", "device_index", "luma_range", "debug"}
+    if unknown:
+        raise TypeError(f"HAVC_deepex: unexpected keyword arguments {sorted(unknown)}")
+    if not isinstance(render_speed, str) or not isinstance(colormap, str):
+        raise HAVCError("HAVC_deepex: render_speed and colormap must be strings")
+    _deepex_checks(clip, clip_ref, method, ref_merge, sc_framedir, only_ref_frames, ex_model, encode_mode, scenes)
+    from .colormnet_render import DEEPEX_SIZES
+    if render_speed.lower() not in DEEPEX_SIZES:
+        raise HAVCError("HAVC_deepex: unknown render_speed ->" + render_speed)                     # deepex/__init__.py:50-83
+    dark_args = smooth_args = None                                                                # __init__.py:1606-1628
+    if dark:
+        dark_args = (dark_p[0], dark_p[1], (dark_p[2] if len(dark_p) > 2 else "none").lower())
+    if smooth:
+        smooth_args = (smooth_p[0], smooth_p[1], smooth_p[2], -smooth_p[3], (smooth_p[4] if len(smooth_p) > 4 else "none").lower())
+    colormap = colormap.lower()
+    colormap_adjust = _get_colormap(colormap) if colormap not in ("none", "") else None
+    if colormap_adjust is not None:
+        try:
+            F.parse_hue_ranges(F.parse_hue_adjust(colormap_adjust)[0])
+        except ValueError:
+            raise HAVCError("HAVC_main: ColorMap choice is invalid for '" + colormap + "'") from None
+    clip, single = _as_clip(clip)
+    clip_ref, _ = _as_clip(clip_ref)
+    n = clip.shape[0]
+    if tuple(clip_ref.shape) != tuple(clip.shape):
+        raise HAVCError(f"HAVC_deepex: clip_ref {tuple(clip_ref.shape)} must have the frames and the size of clip {tuple(clip.shape)}")
+    for f in ("scene_change_prev", "scene_change_next"):
+        if len(getattr(scenes, f)) != n:
+            raise HAVCError(f"HAVC_deepex: scenes.{f} has {len(getattr(scenes, f))} entries for a clip of {n} frames")
+    # ---- everything below touches the GPU ----
+    from . import scdetect
+    from .colormnet_render import DeepExColorMNet
+    from .stabilizer import stabilize_np
+    enable_refmerge = ref_merge > 0 and scenes.sc_frequency == 1                                  # __init__.py:1630-1645
+    dx = DeepExColorMNet(vid_length=n, render_speed=render_speed, enable_resize=False, render_vivid=render_vivid, max_memory_frames=max_memory_frames,
+                         frame_propagate=False, project_dir=torch_dir, state_dict=harness.get("state_dict"), device_index=harness.get("device_index", 0),
+                         network=harness.get("network"))                                          # (max_memory_frames > 0 switches render_vivid off there)
+    ctx = dx.ctx
+    clip_sc = None
+    if enable_refmerge:
+        if ref_weight is None:
+            ref_weight = _REFMERGE_WEIGHT[ref_merge]
+        if ref_thresh is None:
+            ref_thresh = scdetect.DEF_THRESHOLD
+        if ref_freq is None or ref_freq == 1:
+            ref_freq = 0
+        coeffs = scdetect.LUMA_FULL if harness.get("luma_range", "limited") == "full" else scdetect.LUMA_LIMITED
+        clip_sc = scdetect.scene_detect(ctx, clip, threshold=ref_thresh, frequency=ref_freq, frame_norm=ref_norm, coeffs=coeffs)
+    else:
+        ref_weight = 1.0
+    host_in = not is_device(clip)
+    dclip = DeviceImage.from_numpy(ctx, clip) if host_in else clip
+    dref = clip_ref if is_device(clip_ref) else DeviceImage.from_numpy(ctx, clip_ref)
+    merging = 0 < ref_weight < 1 and clip_sc is not None                                          # colormnet/__init__.py:135
+    flags = clip_sc if merging else scenes                                                        # f[2] there, f[1] otherwise
+    ref_small = {}
+
+    def small_ref(i):
+        """clip_ref's frame i at the DeepEx size (SmartResizeReference), tweaked where clip_ref's own props make it a scene change (vs_sc_*)"""
+        if i not in ref_small:
+            sq, _ = dx._squash(dref.frame(i))
+            if (i == 0 or scenes.scene_change_prev[i] == 1) and (dark_args or smooth_args or colormap_adjust):
+                sq = stabilize_np(ctx, sq, dark_args, smooth_args, colormap_adjust, order=("colormap", "dark", "smooth"))      # __init__.py:1679-1689
+            ref_small[i] = sq
+        return ref_small[i]
+
+    out = DeviceImage(ctx, dclip.shape)
+    debug = harness.get("debug")
+    for i in range(n):
+        is_sc = flags.scene_change_prev[i] == 1
+        col = dx.colorize_frame(dclip.frame(i), ref_small=small_ref(i) if (i == 0 or is_sc) else None,
+                                blend=(small_ref(i), ref_weight) if (merging and not is_sc) else None)
+        col = col if is_device(col) else DeviceImage.from_numpy(ctx, np.ascontiguousarray(col))  # (the border path of DeepExColorMNet finishes on the host)
+        out.frame(i).copy_from(col)
+        if debug is None:
+            ref_small.pop(i, None)
+    if debug is not None:
+        debug.update(ref_small=dict(ref_small), clip_sc=clip_sc, ref_weight=ref_weight)
+    if host_in:
+        out = out.numpy()
+        return out[0] if single else out
+    return out.reshaped(out.shape[1:]) if single else out

@@ -87,20 +87,21 @@ def _set_ranges(st, rng):
         st.hue_ranges[i] = v
 
 
-def stabilize_np(ctx, clip, dark=None, smooth=None, colormap=None):
+def stabilize_np(ctx, clip, dark=None, smooth=None, colormap=None, order=("dark", "smooth", "colormap")):
     """HAVC_stabilizer's filters (vsdeoldify/__init__.py:2850-2860) on a frame [h, w, 3] or a clip [n, h, w, 3], ndarray or DeviceImage, in one launch:
          dark     = (dark_threshold, dark_amount[, hue range])                       -> dark_tweak_frame
          smooth   = (black, white, dark_sat, dark_bright[, chroma adjust])           -> chroma_bright_tweak_frame (dark_bright as the filter takes it: <= 0)
          colormap = "chroma adjustment" string                                        -> colormap_frame
-    in that order, None = off; the bytes are those of the three functions called one after the other.  ndarray -> ndarray (blocks), DeviceImage ->
+    in that order (`order`: HAVC_deepex runs colormap first, __init__.py:1679-1689), None = off; the bytes are those of the three functions called one after the other.  ndarray -> ndarray (blocks), DeviceImage ->
     DeviceImage (only enqueues)."""
-    stages = []
+    made = {}
     if dark is not None:
-        stages.append(_dark_stage(*dark))
+        made["dark"] = _dark_stage(*dark)
     if smooth is not None:
-        stages.append(_chroma_stage(smooth[2], smooth[3], smooth[4] if len(smooth) > 4 else "none", (smooth[0], smooth[1])))
+        made["smooth"] = _chroma_stage(smooth[2], smooth[3], smooth[4] if len(smooth) > 4 else "none", (smooth[0], smooth[1]))
     if colormap is not None and colormap != "none":
-        stages.append(_chroma_stage(hue_adjust=colormap))
+        made["colormap"] = _chroma_stage(hue_adjust=colormap)
+    stages = [made[k] for k in order if k in made]
     if is_device(clip):
         a, out = clip, DeviceImage(ctx, clip.shape)
     else:
