@@ -477,6 +477,37 @@ typedef struct havc_scene_rec {
 int havc_scene_stats(havc_ctx* ctx, const uint8_t* clip, const havc_scene_params* params, havc_scene_rec* out);
 /* the normalisation's arithmetic on one value, on the host: k = Y - min, d = max - min -> uint8(255 * (k / d)); d == 0 -> 0.  No context, no GPU. */
 int havc_scene_norm_value(int k, int d);
+/* HAVC_bw_tune (vsdeoldify/__init__.py:1266-1339) and HAVC_auto_levels (:3150-3179 -> havc_utils.py:785-833) on a whole clip [n_frames][height][width][3]:
+ * rgb_balance (havc_utils.py:1087-1145; with balance != 0) and rgb_equalizer (:836-1075), methods 0-3, in two launches (three with balance) that hand their
+ * per-frame results on in device memory.
+ *   method 0  cv2 RGB2YUV, CLAHE(clipLimit = clip_limit, 8 x 8 tiles) on Y, clamp to 16..235 (range_tv) / 0..255, YUV2RGB, image_luma_blend(.., 0.40, 0.90, 0.35, 2.0)
+ *   method 1  cv2.equalizeHist on R, G, B, image_luma_blend(.., 0.40, 0.90, 0.15, 4.0)        method 2  CLAHE on R, G, B, the same blend constants
+ *   method 3  std.Merge(method 0, method 1, weight3)
+ * then std.Merge(result, input, weight) with weight = min(max(1 - strength, 0), 1).  A frame whose f_luma = round(mean(Y) / 255, 6) -- with range_tv
+ * max(round(mean(Y) / 235, 6) - 0.07, 0) -- lies outside [0.15, 0.70] comes back as it went in; luma_blend == 0 takes the equalised frame without the blend.
+ * balance: every channel multiplied by frame_autowhite's gain (from the channel means, round(.., 8), float32 product rounded half to even), then
+ * std.Merge(balanced, input, balance_weight).  std.Merge(a, b, w) = a + (((b - a) * int(w * 32768 + 0.5) + 16384) >> 15).
+ * lut_in is applied to every sample read (in front of balance and equaliser) and lut_out to every sample written: HAVC_bw_tune's std.Levels + range
+ * conversion on the way in and out as one table each (identity tables: none).  OpenCV's steps follow its published algorithm (clahe.cpp, histogram.cpp):
+ * cv2 cannot be executed where the fixtures are made. */
+typedef struct havc_equalize_params {
+    int width, height, n_frames;  /* at least 8 x 8, at most 2^30 pixels per frame */
+    int method;                   /* 0..3 */
+    int luma_blend, range_tv;
+    int balance;
+    int reserved;
+    double clip_limit;            /* 0 = CLAHE without clipping */
+    double weight, weight3, balance_weight;          /* each in [0, 1] */
+    double rgb_factor[3];         /* with balance */
+    uint8_t lut_in[256], lut_out[256];
+} havc_equalize_params;
+/* src, dst: host or device pointers like every filter here; dst must not be src.  Device operands: the call only enqueues.  Integer sums and stated
+ * float sequences throughout: the bytes are identical from run to run. */
+int havc_equalize_clip(havc_ctx* ctx, const uint8_t* src, uint8_t* dst, const havc_equalize_params* params);
+/* the per-frame scalars of the call above, on the host (no context, no GPU): out[0] = f_luma, out[1] = gate (0 / 1), out[2] / out[3] = the blend weight
+ * Image.blend gets for method 0 / for methods 1 and 2 (-1: the equalised frame as it is), out[4..6] = rgb_balance's gains as float32 (1 when chan_sums or
+ * rgb_factor is NULL).  sum_y: sum of cv2's Y over the frame; chan_sums: the three channel sums. */
+int havc_equalize_frame_params(int64_t sum_y, const int64_t* chan_sums, int64_t n_pixels, int range_tv, const double* rgb_factor, double* out);
 /* the per-pixel half of luma_adjusted_levels (vsslib/imfilters.py:335-372): cv2 RGB->YUV, Y' = lut[Y], YUV->RGB.  The caller
  * derives the 256-entry table from havc_image_luma exactly like the reference (vsdeoldify_amd/imfilters.py). */
 int havc_luma_lut(havc_ctx* ctx, const uint8_t* img, const uint8_t* lut256, uint8_t* out, int width, int height);

@@ -79,6 +79,13 @@ class SceneParams(C.Structure):
                 ("bias", C.c_int), ("normalize", C.c_int), ("reserved", C.c_int), ("tht_black", C.c_double), ("tht_white", C.c_double)]
 
 
+class EqualizeParams(C.Structure):
+    """`havc_equalize_params` (include/havc_mi355.h): clip size, method, merge weights, rgb_balance and the in / out tables of havc_equalize_clip"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int), ("method", C.c_int), ("luma_blend", C.c_int), ("range_tv", C.c_int),
+                ("balance", C.c_int), ("reserved", C.c_int), ("clip_limit", C.c_double), ("weight", C.c_double), ("weight3", C.c_double),
+                ("balance_weight", C.c_double), ("rgb_factor", C.c_double * 3), ("lut_in", C.c_uint8 * 256), ("lut_out", C.c_uint8 * 256)]
+
+
 # numpy mirror of `havc_scene_rec`: one record per frame
 SCENE_REC_DTYPE = np.dtype([("sum_y", "<i8"), ("sad", "<i8"), ("sum_raw", "<i8"), ("min_y", "<i4"), ("max_y", "<i4")], align=True)
 
@@ -147,6 +154,8 @@ SYMBOLS = [
     ("havc_tile_reconstruct", _I, [_P, _P, _P, _P, _P]),
     ("havc_scene_stats", _I, [_P, _P, _P, _P]),
     ("havc_scene_norm_value", _I, [_I, _I]),
+    ("havc_equalize_clip", _I, [_P, _P, _P, _P]),
+    ("havc_equalize_frame_params", _I, [C.c_int64, _P, C.c_int64, _I, _P, _P]),
     ("havc_luma_lut", _I, [_P, _P, _P, _P, _I, _I]),
     ("havc_restore_color_gradient", _I, [_P, _P, _P, _P, _I, _I, _D, _I, _D, _D, _I, _I]),
     ("havc_colorize_clip", _I, [_P, _P, _P, _F, _P, _P, _I, _I, _I]),

@@ -3,6 +3,7 @@
 #include "../../include/havc_mi355.h"
 #include "kernels.h"
 #include "scdetect_ops.h"
+#include "equalize_ops.h"
 #include "build_stamp.h"
 
 #include <algorithm>
@@ -988,7 +989,7 @@ static void preload_device_locked(int dev) {
     static uint64_t done = 0;                              // guarded by g_setup_mu
     if (done & (1ull << (dev & 63))) return;
     preload_conv_pipe(); preload_conv_igemm(); preload_elementwise(); preload_zhang(); preload_attention(); preload_colorfilters();
-    preload_tweaks(); preload_stabilizer(); preload_tiles(); preload_scdetect(); preload_ddcolor(); preload_colormnet(); preload_colormnet_net(); preload_precise(); preload_precise2();
+    preload_tweaks(); preload_stabilizer(); preload_tiles(); preload_scdetect(); preload_equalize(); preload_ddcolor(); preload_colormnet(); preload_colormnet_net(); preload_precise(); preload_precise2();
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(scratch_warm_kernel));
     (void)hipGetLastError();
@@ -2100,6 +2101,61 @@ int havc_scene_stats(havc_ctx* c, const uint8_t* clip, const havc_scene_params* 
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < a.n; ++i) out[i].min_y = 255 - out[i].min_y;       // kept as 255 - min on the device (scdetect.hip)
     return HAVC_OK;
+}
+
+// ---- HAVC_bw_tune / HAVC_auto_levels: rgb_balance + rgb_equalizer on a clip (equalize.hip) ----
+static_assert(sizeof(havc_equalize_params) == 600, "havc_equalize_params layout");
+
+int havc_equalize_frame_params(int64_t sum_y, const int64_t* chan_sums, int64_t n_pixels, int range_tv, const double* rgb_factor, double* out) {
+    if (sum_y < 0 || n_pixels <= 0 || !out) return HAVC_E_INVALID;
+    const double fl = eq_f_luma((unsigned long long)sum_y, n_pixels, range_tv);
+    out[0] = fl;
+    out[1] = eq_gate(fl) ? 1.0 : 0.0;
+    out[2] = (double)eq_blend_weight(fl, 0.40, 0.90, 0.35, 2.0);
+    out[3] = (double)eq_blend_weight(fl, 0.40, 0.90, 0.15, 4.0);
+    out[4] = out[5] = out[6] = 1.0;
+    if (chan_sums && rgb_factor) {
+        if (chan_sums[0] < 0 || chan_sums[1] < 0 || chan_sums[2] < 0) return HAVC_E_INVALID;
+        const unsigned long long ch[3] = {(unsigned long long)chan_sums[0], (unsigned long long)chan_sums[1], (unsigned long long)chan_sums[2]};
+        float g[3];
+        eq_balance_gains(ch, n_pixels, rgb_factor, g);
+        for (int k = 0; k < 3; ++k) out[4 + k] = (double)g[k];
+    }
+    return HAVC_OK;
+}
+
+int havc_equalize_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const havc_equalize_params* p) {
+    if (!c || !src || !dst || !p) return fail(c, HAVC_E_INVALID, "equalize_clip: bad args");
+    if (src == dst) return fail(c, HAVC_E_INVALID, "equalize_clip: dst must not be src (the histograms are taken of the whole frame first)");
+    if (p->n_frames <= 0 || p->width < EQ_GRID || p->height < EQ_GRID || (int64_t)p->width * p->height > ((int64_t)1 << 30))
+        return fail(c, HAVC_E_INVALID, "equalize_clip: bad clip size (at least 8 x 8, at most 2^30 pixels per frame)");
+    if (p->method < 0 || p->method > 3) return fail(c, HAVC_E_INVALID, "equalize_clip: method must be 0..3");
+    auto unit = [](double v) { return v >= 0.0 && v <= 1.0; };
+    if (!unit(p->weight) || !unit(p->weight3) || !unit(p->balance_weight)) return fail(c, HAVC_E_INVALID, "equalize_clip: weights must be in [0, 1]");
+    if (!(p->clip_limit >= 0.0 && p->clip_limit <= 1e6)) return fail(c, HAVC_E_INVALID, "equalize_clip: clip_limit must be in [0, 1e6]");
+    for (int k = 0; k < 3; ++k)
+        if (p->balance && !(p->rgb_factor[k] >= 0.0 && p->rgb_factor[k] <= 16.0)) return fail(c, HAVC_E_INVALID, "equalize_clip: rgb_factor must be in [0, 16]");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    EqArgs a{};
+    a.n = p->n_frames; a.h = p->height; a.w = p->width; a.method = p->method;
+    a.luma_blend = p->luma_blend != 0; a.range_tv = p->range_tv != 0; a.balance = p->balance != 0;
+    a.w15 = eq_w15(p->weight); a.w3_15 = eq_w15(p->weight3); a.bal_w15 = eq_w15(p->balance_weight);
+    a.clip_limit = p->clip_limit;
+    for (int k = 0; k < 3; ++k) a.factor[k] = p->rgb_factor[k];
+    memcpy(a.lut_in, p->lut_in, 256);
+    memcpy(a.lut_out, p->lut_out, 256);
+    const size_t cb = (size_t)a.n * a.h * a.w * 3, wb = equalize_workspace_bytes(a.n, a.method);
+    int rc;
+    const uint8_t* d_src;
+    uint8_t* d_dst;
+    bool host;
+    if ((rc = stage_in(c, 0, src, cb, &d_src)) || (rc = stage_out_ptr(c, 2, dst, cb, &d_dst, &host)) || (rc = ensure_scratch(c, 6, wb))) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->scratch[6], 0, (size_t)a.n * (sizeof(EqFrameRec) + 3 * 256 * sizeof(unsigned)), c->stream));
+    const int e = launch_equalize(d_src, d_dst, c->scratch[6], a, c->stream);
+    c->stats.launches += a.balance ? 3 : 2;
+    if (e) return hip_fail(c, (hipError_t)e, "equalize_clip");
+    return stage_out(c, dst, d_dst, cb, host);
 }
 
 int havc_luma_lut(havc_ctx* c, const uint8_t* img, const uint8_t* lut256, uint8_t* out, int width, int height) {

@@ -191,6 +191,19 @@ struct SceneStatsArgs {
     double tht_black, tht_white;
 };
 int launch_scene_stats(const uint8_t* clip, SceneRec* rec, SceneStatsArgs a, hipStream_t s);   // rec: n zero-filled device records
+// equalize.hip: rgb_equalizer methods 0-3 (CLAHE / equalizeHist) with rgb_balance in front, on a clip [n][h][w][3] (vsdeoldify/havc_utils.py:836-1145)
+struct EqArgs {
+    int n, h, w, method;          // method 0..3
+    int luma_blend, range_tv, balance;
+    int w15, w3_15, bal_w15;      // std.Merge weights as int(w * 32768 + 0.5): result <- input, method 0 <- method 1, balanced <- input
+    double clip_limit;
+    double factor[3];             // rgb_balance's rgb_factor
+    uint8_t lut_in[256], lut_out[256];     // applied to every sample read / written
+    int tile_w, tile_h, clip, blocks_per_frame;      // set by launch_equalize
+    float lut_scale;
+};
+size_t equalize_workspace_bytes(int n, int method);
+int launch_equalize(const uint8_t* src, uint8_t* dst, void* ws, EqArgs a, hipStream_t s);   // ws: see equalize.hip
 int launch_restore_color_gradient(const uint8_t* color, const uint8_t* gray, uint8_t* out, int64_t npix, double sat, int tht, double alpha,
                                   double weight, int algo, int return_mask, hipStream_t s);
 // separable polyphase resample of interleaved u8 RGB (tap tables from the host; Spline64 = harness stand-in
@@ -235,6 +248,7 @@ void preload_tweaks();
 void preload_stabilizer();
 void preload_tiles();
 void preload_scdetect();
+void preload_equalize();
 void preload_ddcolor();
 void preload_colormnet();
 void preload_colormnet_net();
