@@ -2,7 +2,7 @@
 
 zimg's `resize.Spline64` (vsdeoldify/__init__.py:2504,3547) stays in the VapourSynth glue in production and
 is OUTSIDE the parity contract.  The bench / clip harness needs *a* resampler on both sides
-of the comparison; this is the CPU twin of the one in csrc/havc_runtime.cpp (get_resize_table) +
+of the comparison; this is the CPU twin of the one in csrc/rt_resize.cpp (get_resize_table) +
 csrc/colorfilters.hip (resize_h_kernel / resize_v_kernel): same taps, horizontal pass first in float32,
 round-half-up to uint8 after the vertical pass, edge replication.
 """

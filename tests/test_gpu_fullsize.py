@@ -106,7 +106,7 @@ def test_generator_raw_color_560(ctx, arch, seed):
 
 
 def test_conv_frame_chunking_is_bit_identical():
-    """Convs whose operands exceed one buffer descriptor run as several frame chunks (havc_runtime.cpp run_op; batch >= 23 at
+    """Convs whose operands exceed one buffer descriptor run as several frame chunks (rt_net.cpp run_op; batch >= 23 at
     560x560).  HAVC_DESC_LIMIT_BYTES lowers the limit of a NEW context so that a 3-frame batch at 96x96 is issued frame by frame
     for the big layers; the bytes must equal the single-launch result."""
     _conv_frame_chunking(str(96 * 96 * 320 * 2 + 4096), None)    # one frame of the 320-pitch tail buffer (+ slack) per launch

@@ -29,6 +29,23 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert lib.havc_version().decode().startswith("havc_mi355")
 
 
+def test_every_prototype_of_the_header_resolves_in_the_built_library():
+    """The runtime is linked from several units (csrc/rt_*.cpp).  A unit dropped from the Makefile's OBJS still links a shared object, and ctypes would
+    only notice when a symbol of that unit is first used: resolve every `havc_*(` prototype of include/havc_mi355.h in a handle of its own, straight from
+    the header and independent of the binding table of _native.py."""
+    nat.load()
+    lib = ctypes.CDLL(nat.LIB_PATH)
+    declared = sorted(set(re.findall(r"\b(havc_[a-z0-9_]+)\s*\(", open(HEADER).read())))
+    assert declared
+    missing = []
+    for name in declared:
+        try:
+            getattr(lib, name)
+        except AttributeError:
+            missing.append(name)
+    assert not missing, f"declared in include/havc_mi355.h but not exported by {nat.LIB_PATH}: {missing}"
+
+
 def test_no_device_fails_loudly():
     lib = nat.load()
     if lib.havc_device_count() > 0:

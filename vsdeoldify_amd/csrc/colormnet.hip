@@ -423,7 +423,7 @@ __global__ void mem_usage_final_kernel(const unsigned long long* __restrict__ ac
 }
 // KeyValueMemoryStore.update_usage in place (kv_memory_store.py:93-101): use_count += usage, life_count += 1, for the elements [from, N)
 // ... and the accumulators go back to zero for the next read (round 5: the launcher no longer clears them with a memset in front of every read; the
-// caller guarantees zeros before the FIRST use of a buffer, havc_runtime.cpp usage_update_locked)
+// caller guarantees zeros before the FIRST use of a buffer, rt_colormnet.cpp usage_update_locked)
 __global__ void mem_usage_update_kernel(unsigned long long* __restrict__ acc, float* __restrict__ use, float* __restrict__ life, int from, int N) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;

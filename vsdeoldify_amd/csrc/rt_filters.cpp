@@ -1,0 +1,370 @@
+// libhavc_mi355.so runtime, filters: the per-pixel filter entry points, tiles, scene statistics and equalisation.
+#include "runtime_internal.h"
+#include "scdetect_ops.h"
+#include "equalize_ops.h"
+
+extern "C" {
+
+int havc_blend(havc_ctx* c, const uint8_t* a, const uint8_t* b, float w, uint8_t* out, int width, int height) {
+    if (!c || !a || !b || !out || width <= 0 || height <= 0) return fail(c, HAVC_E_INVALID, "blend: bad args");
+    const size_t nb = (size_t)width * height * 3;
+    return run_filter(c, a, b, out, nb, "blend", [&](const uint8_t* da, const uint8_t* db, uint8_t* dout) {
+        return launch_blend_u8(da, db, w, dout, (int64_t)nb, c->stream); });
+}
+
+int havc_chroma_post_process(havc_ctx* c, const uint8_t* color, const uint8_t* orig, uint8_t* out, int width, int height) {
+    if (!c || !color || !orig || !out || width <= 0 || height <= 0) return fail(c, HAVC_E_INVALID, "chroma_post_process: bad args");
+    return run_filter(c, color, orig, out, (size_t)width * height * 3, "chroma_post_process", [&](const uint8_t* da, const uint8_t* db, uint8_t* dout) {
+        return launch_yuv_merge(da, db, dout, (int64_t)width * height, c->stream); });
+}
+
+int havc_chroma_stabilizer(havc_ctx* c, const uint8_t* img_stable, const uint8_t* img_new, double alpha, double weight,
+                           uint8_t* out, int width, int height) {
+    if (!c || !img_stable || !img_new || !out || width <= 0 || height <= 0) return fail(c, HAVC_E_INVALID, "chroma_stabilizer: bad args");
+    return run_filter(c, img_stable, img_new, out, (size_t)width * height * 3, "chroma_stabilizer", [&](const uint8_t* da, const uint8_t* db, uint8_t* dout) {
+        return launch_chroma_stabilizer(da, db, alpha, (float)weight, dout, (int64_t)width * height, c->stream); });
+}
+
+int havc_chroma_stabilizer_adaptive(havc_ctx* c, const uint8_t* img_stable, const uint8_t* img_new, double base_tol, double max_extra,
+                                    double weight, uint8_t* out, int width, int height) {
+    if (!c || !img_stable || !img_new || !out || width <= 0 || height <= 0) return fail(c, HAVC_E_INVALID, "chroma_stabilizer_adaptive: bad args");
+    if (out == img_stable) return fail(c, HAVC_E_INVALID, "chroma_stabilizer_adaptive: out must not alias img_stable (Laplacian neighbourhood)");
+    return run_filter(c, img_stable, img_new, out, (size_t)width * height * 3, "chroma_stabilizer_adaptive", [&](const uint8_t* da, const uint8_t* db, uint8_t* dout) {
+        return launch_chroma_stabilizer_adaptive(da, db, (float)base_tol, (float)max_extra, (float)weight, dout, width, height, c->stream); });
+}
+
+int havc_chroma_temporal_limiter(havc_ctx* c, const uint8_t* cur, const uint8_t* prv, double alpha, uint8_t* out, int width, int height) {
+    if (!c || !cur || !prv || !out || width <= 0 || height <= 0) return fail(c, HAVC_E_INVALID, "chroma_temporal_limiter: bad args");
+    return run_filter(c, cur, prv, out, (size_t)width * height * 3, "chroma_temporal_limiter", [&](const uint8_t* da, const uint8_t* db, uint8_t* dout) {
+        return launch_chroma_temporal_limiter(da, db, alpha, dout, (int64_t)width * height, c->stream); });
+}
+
+int havc_image_luma_merge(havc_ctx* c, const uint8_t* img_dark, const uint8_t* img_white, int mode, double tresh, double grad, uint8_t* out,
+                          int width, int height) {
+    if (!c || !img_dark || !img_white || !out || width <= 0 || height <= 0 || mode < 0 || mode > 3) return fail(c, HAVC_E_INVALID, "image_luma_merge: bad args");
+    return run_filter(c, img_dark, img_white, out, (size_t)width * height * 3, "image_luma_merge", [&](const uint8_t* da, const uint8_t* db, uint8_t* dout) {
+        return launch_luma_merge(da, db, mode, tresh, grad, dout, (int64_t)width * height, c->stream); });
+}
+
+int havc_image_luma(havc_ctx* c, const uint8_t* img, int width, int height, double* mean_y) {
+    if (!c || !img || !mean_y || width <= 0 || height <= 0) return fail(c, HAVC_E_INVALID, "image_luma: bad args");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    const size_t nb = (size_t)width * height * 3;
+    int rc;
+    const uint8_t* din;
+    if ((rc = stage_in(c, SCR_IN, img, nb, &din)) || (rc = ensure_scratch(c, SCR_SMALL, 256))) return rc;
+    int e = launch_luma_sum(din, (unsigned long long*)c->scratch[SCR_SMALL], (int64_t)width * height, c->stream);
+    c->stats.launches++;
+    if (e) return hip_fail(c, (hipError_t)e, "luma sum");
+    unsigned long long sum = 0;
+    HIP_TRY(c, hipMemcpyAsync(&sum, c->scratch[SCR_SMALL], sizeof(sum), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *mean_y = (double)sum / ((double)width * (double)height);
+    return HAVC_OK;
+}
+
+int havc_image_tweak(havc_ctx* c, const uint8_t* img, uint8_t* out, int width, int height, int hue_offset, float brightness, float contrast,
+                     float color, const double* hue_ranges, int n_ranges) {
+    if (!c || !img || !out || width <= 0 || height <= 0 || n_ranges < 0 || n_ranges > HAVC_MAX_HUE_RANGES || (n_ranges && !hue_ranges))
+        return fail(c, HAVC_E_INVALID, "image_tweak: bad args (at most 8 hue ranges)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    const size_t nb = (size_t)width * height * 3;
+    const int64_t npix = (int64_t)width * height;
+    int rc;
+    const uint8_t* din;
+    uint8_t* dout;
+    bool host;
+    if ((rc = stage_in(c, SCR_IN, img, nb, &din)) || (rc = stage_out_ptr(c, SCR_OUT, out, nb, &dout, &host)) || (rc = ensure_scratch(c, SCR_SMALL, 256))) return rc;
+    TweakArgs a{};
+    a.hue_offset = hue_offset; a.brightness = brightness; a.contrast = contrast; a.color = color; a.mean_l = 0; a.n_ranges = n_ranges;
+    for (int k = 0; k < n_ranges; ++k) { a.range_lo[k] = hue_ranges[2 * k]; a.range_hi[k] = hue_ranges[2 * k + 1]; }
+    if (contrast != 1.f) {
+        // ImageEnhance.Contrast: degenerate = solid int(mean(L) + 0.5) of the image as it enters the step
+        int e = launch_image_tweak(din, dout, npix, a, (unsigned long long*)c->scratch[SCR_SMALL], true, c->stream);
+        c->stats.launches++;
+        if (e) return hip_fail(c, (hipError_t)e, "image_tweak (L sum)");
+        unsigned long long sum = 0;
+        HIP_TRY(c, hipMemcpyAsync(&sum, c->scratch[SCR_SMALL], sizeof(sum), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        a.mean_l = (int)((double)sum / (double)npix + 0.5);
+    }
+    int e = launch_image_tweak(din, dout, npix, a, (unsigned long long*)c->scratch[SCR_SMALL], false, c->stream);
+    c->stats.launches++;
+    if (e) return hip_fail(c, (hipError_t)e, "image_tweak");
+    return stage_out(c, out, dout, nb, host);
+}
+
+// the argument normalisation of np_image_chroma_tweak (restcolor.py:288-350): clamps, half-degree hue steps, which sub-steps run
+static ChromaTweakArgs chroma_tweak_args(double sat, double bright, int hue, int has_adjust, const double* hue_ranges, int n_ranges, double adj_sat,
+                                         int adj_hue, double adj_weight) {
+    auto clampd = [](double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); };
+    ChromaTweakArgs a{};
+    a.has_hue = hue != 0; a.hue_half = 0.5 * (double)std::min(std::max(hue, -360), 360);
+    a.satc = clampd(sat, 0.0, 10.0); a.brightc = clampd(1.0 + bright, 0.0, 10.0);
+    a.has_adjust = has_adjust == 2 ? 2 : (has_adjust != 0); a.n_ranges = has_adjust ? n_ranges : 0;
+    if (has_adjust == 2) { a.has_hue = 0; a.satc = 1.0; a.brightc = 1.0; }
+    for (int k = 0; k < a.n_ranges; ++k) { a.range_lo[k] = hue_ranges[2 * k]; a.range_hi[k] = hue_ranges[2 * k + 1]; }
+    a.has_hue2 = adj_hue != 0; a.hue_half2 = 0.5 * (double)std::min(std::max(adj_hue, -360), 360);
+    a.has_sat2 = adj_sat != 1.0; a.sat2c = clampd(adj_sat, 0.0, 10.0);
+    a.weight = adj_weight;
+    return a;
+}
+
+int havc_image_chroma_tweak(havc_ctx* c, const uint8_t* img, uint8_t* out, int width, int height, double sat, double bright, int hue,
+                            int has_adjust, const double* hue_ranges, int n_ranges, double adj_sat, int adj_hue, double adj_weight) {
+    if (!c || !img || !out || width <= 0 || height <= 0 || n_ranges < 0 || n_ranges > HAVC_MAX_HUE_RANGES || (has_adjust && (!hue_ranges || n_ranges < 1)))
+        return fail(c, HAVC_E_INVALID, "image_chroma_tweak: bad args (1..8 hue ranges with an adjust stage)");
+    const ChromaTweakArgs a = chroma_tweak_args(sat, bright, hue, has_adjust, hue_ranges, n_ranges, adj_sat, adj_hue, adj_weight);
+    return run_filter(c, img, nullptr, out, (size_t)width * height * 3, "image_chroma_tweak", [&](const uint8_t* da, const uint8_t*, uint8_t* dout) {
+        return launch_chroma_tweak(da, dout, (int64_t)width * height, a, c->stream); });
+}
+
+int havc_stabilizer_chain(havc_ctx* c, const uint8_t* img, uint8_t* out, int width, int height, const havc_stab_stage* stages, int n_stages) {
+    if (!c || !img || !out || width <= 0 || height <= 0 || n_stages < 0 || n_stages > HAVC_MAX_STAB_STAGES || (n_stages && !stages))
+        return fail(c, HAVC_E_INVALID, "stabilizer_chain: bad args (0..3 stages)");
+    StabChainArgs a{};
+    a.n = n_stages;
+    for (int i = 0; i < n_stages; ++i) {
+        const havc_stab_stage& s = stages[i];
+        if (s.kind < 0 || s.kind > 1 || s.merge_mode < -1 || s.merge_mode > 3 || s.n_ranges < 0 || s.n_ranges > HAVC_MAX_HUE_RANGES ||
+            (s.kind == 1 && (s.has_adjust < 0 || s.has_adjust > 1 || (s.has_adjust && s.n_ranges < 1))))
+            return fail(c, HAVC_E_INVALID, "stabilizer_chain: bad stage (kind 0 / 1, merge_mode -1..3, at most 8 hue ranges, 1..8 with an adjust stage)");
+        StabStage& d = a.st[i];
+        d.kind = s.kind; d.identity = s.kind == 1 && s.identity; d.merge_mode = s.merge_mode; d.tresh = s.tresh; d.grad = s.grad;
+        if (s.kind == 0) {
+            d.tw.hue_offset = s.hue_offset; d.tw.brightness = s.brightness; d.tw.contrast = 1.f; d.tw.color = s.color; d.tw.mean_l = 0;
+            d.tw.n_ranges = s.n_ranges;
+            for (int k = 0; k < s.n_ranges; ++k) { d.tw.range_lo[k] = s.hue_ranges[2 * k]; d.tw.range_hi[k] = s.hue_ranges[2 * k + 1]; }
+        } else {
+            d.ct = chroma_tweak_args(s.sat, s.bright, s.hue, s.has_adjust, s.hue_ranges, s.n_ranges, s.adj_sat, s.adj_hue, s.adj_weight);
+        }
+    }
+    const size_t nb = (size_t)width * height * 3;
+    return run_filter(c, img, nullptr, out, nb, "stabilizer_chain", [&](const uint8_t* da, const uint8_t*, uint8_t* dout) {
+        if (a.n == 0) return da == dout ? 0 : (int)hipMemcpyAsync(dout, da, nb, hipMemcpyDeviceToDevice, c->stream);
+        return launch_stabilizer_chain(da, dout, (int64_t)width * height, a, c->stream); });
+}
+
+// ---- HAVC_clip_slice / HAVC_clip_reconstruct (tiles.hip) ----
+// what keeps every read and write of the two kernels inside its buffer: the tiles cover the clip, the overlaps are smaller than the base tile
+static const char* tile_geom_error(const havc_tile_geom* g) {
+    if (!g || g->width <= 0 || g->height <= 0 || g->n_frames <= 0) return "bad args";
+    if (g->n_tiles != 2 && g->n_tiles != 4) return "n_tiles must be 2 or 4";
+    if (g->base_w <= 0 || g->base_h <= 0 || g->width > 2 * g->base_w) return "the tiles do not cover the clip's width";
+    if (g->n_tiles == 4 ? g->height > 2 * g->base_h : (g->height != g->base_h || g->overlap_y != 0))
+        return "the tiles do not cover the clip's height (2 tiles: base_h = height, overlap_y = 0)";
+    if (g->overlap_x < 0 || g->overlap_y < 0 || g->overlap_x >= g->base_w || (g->n_tiles == 4 && g->overlap_y >= g->base_h))
+        return "an overlap must be >= 0 and smaller than the base tile";
+    if (g->mask_val < 0 || g->mask_val > 255) return "mask_val must be 0..255";
+    return nullptr;
+}
+static TileArgs tile_args(const havc_tile_geom* g) {
+    TileArgs a{};
+    a.w = g->width; a.h = g->height; a.n = g->n_frames; a.n_tiles = g->n_tiles;
+    a.base_w = g->base_w; a.base_h = g->base_h; a.ox = g->overlap_x; a.oy = g->overlap_y; a.mask_val = g->mask_val;
+    return a;
+}
+static size_t tile_stage_bytes(size_t n) { return (n + 255) & ~(size_t)255; }
+
+int havc_tile_slice(havc_ctx* c, const uint8_t* clip, uint8_t* const* tiles, const havc_tile_geom* g) {
+    if (!c || !clip || !tiles) return fail(c, HAVC_E_INVALID, "tile_slice: bad args");
+    if (const char* why = tile_geom_error(g)) return fail(c, HAVC_E_INVALID, (std::string("tile_slice: ") + why).c_str());
+    for (int t = 0; t < g->n_tiles; ++t) if (!tiles[t]) return fail(c, HAVC_E_INVALID, "tile_slice: NULL tile");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    TileArgs a = tile_args(g);
+    const size_t cb = (size_t)a.n * a.h * a.w * 3, tb = (size_t)a.n * (a.base_h + a.oy) * (a.base_w + a.ox) * 3;
+    int rc, n_host = 0;
+    bool host[4] = {false, false, false, false};
+    for (int t = 0; t < a.n_tiles; ++t) n_host += (host[t] = !is_device_ptr(tiles[t]));
+    const uint8_t* d_clip;
+    if ((rc = stage_in(c, SCR_IN, clip, cb, &d_clip)) || (n_host && (rc = ensure_scratch(c, SCR_OUT, tile_stage_bytes(tb) * n_host)))) return rc;
+    for (int t = 0, k = 0; t < a.n_tiles; ++t) a.tile[t] = host[t] ? (uint8_t*)c->scratch[SCR_OUT] + tile_stage_bytes(tb) * k++ : tiles[t];
+    const int e = launch_tile_slice(d_clip, a, c->stream);
+    c->stats.launches++;
+    if (e) return hip_fail(c, (hipError_t)e, "tile_slice");
+    for (int t = 0; t < a.n_tiles; ++t)
+        if (host[t]) HIP_TRY(c, hipMemcpyAsync(tiles[t], a.tile[t], tb, hipMemcpyDeviceToHost, c->stream));
+    if (n_host) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HAVC_OK;
+}
+
+int havc_tile_reconstruct(havc_ctx* c, const uint8_t* const* tiles, const uint8_t* clip_orig, uint8_t* out, const havc_tile_geom* g) {
+    if (!c || !tiles || !out) return fail(c, HAVC_E_INVALID, "tile_reconstruct: bad args");
+    if (const char* why = tile_geom_error(g)) return fail(c, HAVC_E_INVALID, (std::string("tile_reconstruct: ") + why).c_str());
+    if (g->recover_luma && !clip_orig) return fail(c, HAVC_E_INVALID, "tile_reconstruct: recover_luma needs clip_orig");
+    for (int t = 0; t < g->n_tiles; ++t)
+        if (!tiles[t] || tiles[t] == out) return fail(c, HAVC_E_INVALID, "tile_reconstruct: NULL tile, or out is a tile");
+    if (g->recover_luma && clip_orig == out) return fail(c, HAVC_E_INVALID, "tile_reconstruct: out must not be clip_orig");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    TileArgs a = tile_args(g);
+    const size_t cb = (size_t)a.n * a.h * a.w * 3, tb = (size_t)a.n * (a.base_h + a.oy) * (a.base_w + a.ox) * 3;
+    const uint8_t* orig = g->recover_luma ? clip_orig : nullptr;
+    // host operands share one staging buffer (SCR_IN), sized before the first copy into it
+    size_t need = 0;
+    for (int t = 0; t < a.n_tiles; ++t) if (!is_device_ptr(tiles[t])) need += tile_stage_bytes(tb);
+    if (orig && !is_device_ptr(orig)) need += tile_stage_bytes(cb);
+    int rc;
+    uint8_t* dout;
+    bool host_out;
+    if ((need && (rc = ensure_scratch(c, SCR_IN, need))) || (rc = stage_out_ptr(c, SCR_OUT, out, cb, &dout, &host_out))) return rc;
+    size_t at = 0;
+    auto staged = [&](const uint8_t* p, size_t nb, const uint8_t** d) -> int {
+        if (is_device_ptr(p)) { *d = p; return HAVC_OK; }
+        uint8_t* dst = (uint8_t*)c->scratch[SCR_IN] + at;
+        at += tile_stage_bytes(nb);
+        HIP_TRY(c, hipMemcpyAsync(dst, p, nb, hipMemcpyHostToDevice, c->stream));
+        *d = dst;
+        return HAVC_OK;
+    };
+    for (int t = 0; t < a.n_tiles; ++t) {
+        const uint8_t* d;
+        if ((rc = staged(tiles[t], tb, &d))) return rc;
+        a.tile[t] = const_cast<uint8_t*>(d);
+    }
+    if (orig && (rc = staged(orig, cb, &orig))) return rc;
+    const int e = launch_tile_reconstruct(a, orig, dout, c->stream);
+    c->stats.launches++;
+    if (e) return hip_fail(c, (hipError_t)e, "tile_reconstruct");
+    return stage_out(c, out, dout, cb, host_out);
+}
+
+// ---- HAVC_SceneDetect's per-frame statistics (scdetect.hip) ----
+static_assert(sizeof(SceneRec) == sizeof(havc_scene_rec) && sizeof(havc_scene_rec) == 32, "havc_scene_rec layout");
+
+int havc_scene_norm_value(int k, int d) { return scene_norm_value(k, d); }
+
+int havc_scene_stats(havc_ctx* c, const uint8_t* clip, const havc_scene_params* p, havc_scene_rec* out) {
+    if (!c || !clip || !p || !out) return fail(c, HAVC_E_INVALID, "scene_stats: bad args");
+    if (p->width <= 0 || p->height <= 0 || p->n_frames <= 0 || (int64_t)p->width * p->height > ((int64_t)1 << 31))
+        return fail(c, HAVC_E_INVALID, "scene_stats: bad clip size (at most 2^31 pixels per frame)");
+    if (p->offset < 1 || p->offset > 25) return fail(c, HAVC_E_INVALID, "scene_stats: offset must be 1..25");
+    if (p->cr < 0 || p->cg < 0 || p->cb < 0 || p->bias < 0 || ((int64_t)p->cr + p->cg + p->cb) * 255 + p->bias >= ((int64_t)256 << 16))
+        return fail(c, HAVC_E_INVALID, "scene_stats: luma coefficients must be >= 0 and keep Y = (cr*R + cg*G + cb*B + bias) >> 16 below 256");
+    if (p->normalize && !(p->tht_black >= 0.0 && p->tht_white <= 1.0 && p->tht_black <= p->tht_white))
+        return fail(c, HAVC_E_INVALID, "scene_stats: normalize needs 0 <= tht_black <= tht_white <= 1");
+    if (is_device_ptr(out)) return fail(c, HAVC_E_INVALID, "scene_stats: the records are downloaded: out must be host memory");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    SceneStatsArgs a{};
+    a.n = p->n_frames; a.h = p->height; a.w = p->width; a.offset = p->offset;
+    a.cr = p->cr; a.cg = p->cg; a.cb = p->cb; a.bias = p->bias;
+    a.normalize = p->normalize != 0; a.tht_black = p->tht_black; a.tht_white = p->tht_white;
+    const size_t cb = (size_t)a.n * a.h * a.w * 3, rb = (size_t)a.n * sizeof(SceneRec);
+    int rc;
+    const uint8_t* d_clip;
+    if ((rc = stage_in(c, SCR_IN, clip, cb, &d_clip)) || (rc = ensure_scratch(c, SCR_SMALL, rb))) return rc;
+    SceneRec* d_rec = (SceneRec*)c->scratch[SCR_SMALL];
+    HIP_TRY(c, hipMemsetAsync(d_rec, 0, rb, c->stream));
+    const int e = launch_scene_stats(d_clip, d_rec, a, c->stream);
+    c->stats.launches += a.normalize ? 2 : 1;
+    if (e) return hip_fail(c, (hipError_t)e, "scene_stats");
+    HIP_TRY(c, hipMemcpyAsync(out, d_rec, rb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < a.n; ++i) out[i].min_y = 255 - out[i].min_y;       // kept as 255 - min on the device (scdetect.hip)
+    return HAVC_OK;
+}
+
+// ---- HAVC_bw_tune / HAVC_auto_levels: rgb_balance + rgb_equalizer on a clip (equalize.hip) ----
+static_assert(sizeof(havc_equalize_params) == 600, "havc_equalize_params layout");
+
+int havc_equalize_frame_params(int64_t sum_y, const int64_t* chan_sums, int64_t n_pixels, int range_tv, const double* rgb_factor, double* out) {
+    if (sum_y < 0 || n_pixels <= 0 || !out) return HAVC_E_INVALID;
+    const double fl = eq_f_luma((unsigned long long)sum_y, n_pixels, range_tv);
+    out[0] = fl;
+    out[1] = eq_gate(fl) ? 1.0 : 0.0;
+    out[2] = (double)eq_blend_weight(fl, 0.40, 0.90, 0.35, 2.0);
+    out[3] = (double)eq_blend_weight(fl, 0.40, 0.90, 0.15, 4.0);
+    out[4] = out[5] = out[6] = 1.0;
+    if (chan_sums && rgb_factor) {
+        if (chan_sums[0] < 0 || chan_sums[1] < 0 || chan_sums[2] < 0) return HAVC_E_INVALID;
+        const unsigned long long ch[3] = {(unsigned long long)chan_sums[0], (unsigned long long)chan_sums[1], (unsigned long long)chan_sums[2]};
+        float g[3];
+        eq_balance_gains(ch, n_pixels, rgb_factor, g);
+        for (int k = 0; k < 3; ++k) out[4 + k] = (double)g[k];
+    }
+    return HAVC_OK;
+}
+
+int havc_equalize_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const havc_equalize_params* p) {
+    if (!c || !src || !dst || !p) return fail(c, HAVC_E_INVALID, "equalize_clip: bad args");
+    if (src == dst) return fail(c, HAVC_E_INVALID, "equalize_clip: dst must not be src (the histograms are taken of the whole frame first)");
+    if (p->n_frames <= 0 || p->width < EQ_GRID || p->height < EQ_GRID || (int64_t)p->width * p->height > ((int64_t)1 << 30))
+        return fail(c, HAVC_E_INVALID, "equalize_clip: bad clip size (at least 8 x 8, at most 2^30 pixels per frame)");
+    if (p->method < 0 || p->method > 3) return fail(c, HAVC_E_INVALID, "equalize_clip: method must be 0..3");
+    auto unit = [](double v) { return v >= 0.0 && v <= 1.0; };
+    if (!unit(p->weight) || !unit(p->weight3) || !unit(p->balance_weight)) return fail(c, HAVC_E_INVALID, "equalize_clip: weights must be in [0, 1]");
+    if (!(p->clip_limit >= 0.0 && p->clip_limit <= 1e6)) return fail(c, HAVC_E_INVALID, "equalize_clip: clip_limit must be in [0, 1e6]");
+    for (int k = 0; k < 3; ++k)
+        if (p->balance && !(p->rgb_factor[k] >= 0.0 && p->rgb_factor[k] <= 16.0)) return fail(c, HAVC_E_INVALID, "equalize_clip: rgb_factor must be in [0, 16]");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    EqArgs a{};
+    a.n = p->n_frames; a.h = p->height; a.w = p->width; a.method = p->method;
+    a.luma_blend = p->luma_blend != 0; a.range_tv = p->range_tv != 0; a.balance = p->balance != 0;
+    a.w15 = eq_w15(p->weight); a.w3_15 = eq_w15(p->weight3); a.bal_w15 = eq_w15(p->balance_weight);
+    a.clip_limit = p->clip_limit;
+    for (int k = 0; k < 3; ++k) a.factor[k] = p->rgb_factor[k];
+    memcpy(a.lut_in, p->lut_in, 256);
+    memcpy(a.lut_out, p->lut_out, 256);
+    const size_t cb = (size_t)a.n * a.h * a.w * 3, wb = equalize_workspace_bytes(a.n, a.method);
+    int rc;
+    const uint8_t* d_src;
+    uint8_t* d_dst;
+    bool host;
+    if ((rc = stage_in(c, SCR_IN, src, cb, &d_src)) || (rc = stage_out_ptr(c, SCR_OUT, dst, cb, &d_dst, &host)) || (rc = ensure_scratch(c, SCR_SMALL, wb))) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->scratch[SCR_SMALL], 0, (size_t)a.n * (sizeof(EqFrameRec) + 3 * 256 * sizeof(unsigned)), c->stream));
+    const int e = launch_equalize(d_src, d_dst, c->scratch[SCR_SMALL], a, c->stream);
+    c->stats.launches += a.balance ? 3 : 2;
+    if (e) return hip_fail(c, (hipError_t)e, "equalize_clip");
+    return stage_out(c, dst, d_dst, cb, host);
+}
+
+int havc_luma_lut(havc_ctx* c, const uint8_t* img, const uint8_t* lut256, uint8_t* out, int width, int height) {
+    if (!c || !img || !lut256 || !out || width <= 0 || height <= 0) return fail(c, HAVC_E_INVALID, "luma_lut: bad args");
+    return run_filter(c, img, nullptr, out, (size_t)width * height * 3, "luma_lut",
+                      [&](const uint8_t* da, const uint8_t*, uint8_t* dout) {
+                          return launch_luma_lut(da, (const uint8_t*)c->scratch[SCR_SMALL], dout, (int64_t)width * height, c->stream); },
+                      [&]() -> int {
+                          int rc = ensure_scratch(c, SCR_SMALL, 256);
+                          if (rc) return rc;
+                          HIP_TRY(c, hipMemcpyAsync(c->scratch[SCR_SMALL], lut256, 256, hipMemcpyDefault, c->stream));
+                          return HAVC_OK; });
+}
+
+int havc_restore_color_gradient(havc_ctx* c, const uint8_t* img_color, const uint8_t* img_gray, uint8_t* out, int width, int height, double sat,
+                                int tht, double weight, double alpha, int algo, int return_mask) {
+    if (!c || !img_color || !img_gray || !out || width <= 0 || height <= 0 || algo < 0 || algo > 2)
+        return fail(c, HAVC_E_INVALID, "restore_color_gradient: bad args (algo 0..2)");
+    return run_filter(c, img_color, img_gray, out, (size_t)width * height * 3, "restore_color_gradient", [&](const uint8_t* da, const uint8_t* db, uint8_t* dout) {
+        return launch_restore_color_gradient(da, db, dout, (int64_t)width * height, sat, tht, alpha, weight, algo, return_mask, c->stream); });
+}
+
+int havc_color_temporal_stabilizer(havc_ctx* c, const uint8_t* const* frames, const double* weights, int n, uint8_t* out, int width, int height) {
+    if (!c || !frames || !weights || !out || n < 1 || n > 9 || width <= 0 || height <= 0) return fail(c, HAVC_E_INVALID, "color_temporal_stabilizer: bad args (1..9 frames)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    const size_t nb = (size_t)width * height * 3;
+    int rc;
+    if ((rc = ensure_scratch(c, SCR_IN, nb * n))) return rc;
+    uint8_t* dout;
+    bool host;
+    if ((rc = stage_out_ptr(c, SCR_OUT, out, nb, &dout, &host))) return rc;
+    const uint8_t* d_frames[9];
+    for (int k = 0; k < n; ++k) {
+        if (!frames[k]) return fail(c, HAVC_E_INVALID, "color_temporal_stabilizer: NULL frame");
+        if (is_device_ptr(frames[k])) { d_frames[k] = frames[k]; continue; }
+        uint8_t* d = (uint8_t*)c->scratch[SCR_IN] + nb * k;
+        HIP_TRY(c, hipMemcpyAsync(d, frames[k], nb, hipMemcpyHostToDevice, c->stream));
+        d_frames[k] = d;
+    }
+    int e = launch_color_temporal_stabilizer(d_frames, weights, n, dout, (int64_t)width * height, c->stream);
+    c->stats.launches++;
+    if (e) return hip_fail(c, (hipError_t)e, "color_temporal_stabilizer");
+    return stage_out(c, out, dout, nb, host);
+}
+
+}  // extern "C"

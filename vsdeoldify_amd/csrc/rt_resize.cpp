@@ -1,0 +1,171 @@
+// libhavc_mi355.so runtime, resampling: the Spline64 and Pillow coefficient tables and their resize entry points.
+#include "runtime_internal.h"
+
+namespace {
+
+// ---- Spline64 polyphase tables (Avisynth/zimg Spline64 kernel, support 4, widened when downscaling) ----
+double spline64(double x) {
+    x = std::fabs(x);
+    if (x < 1.0) return ((49.0 / 41.0 * x - 6387.0 / 2911.0) * x - 3.0 / 2911.0) * x + 1.0;
+    if (x < 2.0) { x -= 1.0; return ((-24.0 / 41.0 * x + 4032.0 / 2911.0) * x - 2328.0 / 2911.0) * x; }
+    if (x < 3.0) { x -= 2.0; return ((6.0 / 41.0 * x - 1008.0 / 2911.0) * x + 582.0 / 2911.0) * x; }
+    if (x < 4.0) { x -= 3.0; return ((-1.0 / 41.0 * x + 168.0 / 2911.0) * x - 97.0 / 2911.0) * x; }
+    return 0.0;
+}
+
+int get_resize_table(havc_ctx* c, int src, int dst, ResizeTable** out) {
+    auto key = std::make_pair(src, dst);
+    auto it = c->resize_tables.find(key);
+    if (it != c->resize_tables.end()) { *out = &it->second; return HAVC_OK; }
+    const double scale = (double)dst / (double)src;
+    const double fscale = scale < 1.0 ? scale : 1.0;       // kernel stretch for anti-aliasing
+    const double support = 4.0 / fscale;
+    const int taps = (int)std::ceil(2.0 * support) + 1;
+    std::vector<int> start(dst);
+    std::vector<float> w((size_t)dst * taps);
+    for (int i = 0; i < dst; ++i) {
+        const double center = (i + 0.5) / scale - 0.5;
+        const int s0 = (int)std::floor(center - support) + 1;
+        double sum = 0;
+        std::vector<double> tmp(taps);
+        for (int t = 0; t < taps; ++t) { tmp[t] = spline64((s0 + t - center) * fscale); sum += tmp[t]; }
+        for (int t = 0; t < taps; ++t) w[(size_t)i * taps + t] = (float)(tmp[t] / sum);
+        start[i] = s0;
+    }
+    ResizeTable tb;
+    tb.taps = taps;
+    SetupLock setup;
+    HIP_TRY(c, hipMalloc((void**)&tb.d_start, dst * sizeof(int)));
+    HIP_TRY(c, hipMalloc((void**)&tb.d_w, w.size() * sizeof(float)));
+    HIP_TRY(c, hipMemcpy(tb.d_start, start.data(), dst * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(tb.d_w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+    auto res = c->resize_tables.emplace(key, tb);
+    *out = &res.first->second;
+    return HAVC_OK;
+}
+
+}  // namespace
+
+int resize_rgb8(havc_ctx* c, const uint8_t* d_src, int sw, int sh, uint8_t* d_dst, int dw, int dh, int n,
+                const uint8_t* d_orig) {
+    ResizeTable *th, *tv;
+    int rc = get_resize_table(c, sw, dw, &th);
+    if (rc) return rc;
+    rc = get_resize_table(c, sh, dh, &tv);
+    if (rc) return rc;
+    rc = ensure_scratch(c, SCR_RESIZE_ROWS, (size_t)n * sh * dw * 3 * sizeof(float));
+    if (rc) return rc;
+    int e = launch_resize_passes(d_src, sw, sh, d_dst, dw, dh, n, (float*)c->scratch[SCR_RESIZE_ROWS], th->d_start, th->d_w, th->taps,
+                                 tv->d_start, tv->d_w, tv->taps, d_orig, c->stream);
+    c->stats.launches += 2;
+    if (e) return hip_fail(c, (hipError_t)e, "resize");
+    return HAVC_OK;
+}
+
+namespace {
+
+// ---- Pillow ImagingResample coefficient tables (libImaging/Resample.c precompute_coeffs + normalize_coeffs_8bpc) ----
+struct PilTable { int ksize = 0; int* d_bounds = nullptr; int* d_kk = nullptr; };
+
+double pil_filter(int resample, double x) {
+    if (x < 0.0) x = -x;
+    if (resample == 2) return x < 1.0 ? 1.0 - x : 0.0;                       // BILINEAR
+    const double a = -0.5;                                                    // BICUBIC
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
+
+int build_pil_table(havc_ctx* c, int in_size, int out_size, int resample, PilTable* tb) {
+    const double fsupport = resample == 2 ? 1.0 : 2.0;
+    const double scale = (double)in_size / (double)out_size;
+    double filterscale = scale < 1.0 ? 1.0 : scale;
+    const double support = fsupport * filterscale;
+    const int ksize = (int)std::ceil(support) * 2 + 1;
+    std::vector<int> bounds(out_size * 2), kk((size_t)out_size * ksize, 0);
+    std::vector<double> w(ksize);
+    const double ss = 1.0 / filterscale;
+    for (int xx = 0; xx < out_size; ++xx) {
+        const double center = (xx + 0.5) * scale;
+        int xmin = (int)(center - support + 0.5);
+        if (xmin < 0) xmin = 0;
+        int xmax = (int)(center + support + 0.5);
+        if (xmax > in_size) xmax = in_size;
+        xmax -= xmin;
+        double ww = 0.0;
+        for (int x = 0; x < xmax; ++x) { w[x] = pil_filter(resample, (x + xmin - center + 0.5) * ss); ww += w[x]; }
+        for (int x = 0; x < xmax; ++x) {
+            const double v = ww != 0.0 ? w[x] / ww : w[x];
+            kk[(size_t)xx * ksize + x] = v < 0 ? (int)(-0.5 + v * (double)(1 << 22)) : (int)(0.5 + v * (double)(1 << 22));
+        }
+        bounds[xx * 2] = xmin; bounds[xx * 2 + 1] = xmax;
+    }
+    tb->ksize = ksize;
+    SetupLock setup;
+    HIP_TRY(c, hipMalloc((void**)&tb->d_bounds, bounds.size() * sizeof(int)));
+    HIP_TRY(c, hipMalloc((void**)&tb->d_kk, kk.size() * sizeof(int)));
+    HIP_TRY(c, hipMemcpy(tb->d_bounds, bounds.data(), bounds.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(tb->d_kk, kk.data(), kk.size() * sizeof(int), hipMemcpyHostToDevice));
+    return HAVC_OK;
+}
+
+void free_pil_table(PilTable& t) { if (t.d_bounds) (void)hipFree(t.d_bounds); if (t.d_kk) (void)hipFree(t.d_kk); t = PilTable{}; }
+
+}  // namespace
+
+// Image.resize on device buffers; tmp must hold n*sh*dw*3 bytes
+int pil_resize_dev(havc_ctx* c, const uint8_t* d_src, int sw, int sh, uint8_t* d_tmp, uint8_t* d_dst, int dw, int dh, int n, int resample) {
+    PilTable th, tv;
+    int rc = HAVC_OK;
+    if (sw != dw && (rc = build_pil_table(c, sw, dw, resample, &th))) return rc;
+    if (sh != dh && (rc = build_pil_table(c, sh, dh, resample, &tv))) { free_pil_table(th); return rc; }
+    int e = launch_pil_resize_passes(d_src, sw, sh, d_tmp, d_dst, dw, dh, n, th.d_bounds, th.d_kk, th.ksize, tv.d_bounds, tv.d_kk,
+                                     tv.ksize, c->stream);
+    c->stats.launches += 2;
+    hipError_t se = hipStreamSynchronize(c->stream);       // tables are freed right away (tiny, rebuilt per call)
+    free_pil_table(th); free_pil_table(tv);
+    if (e) return hip_fail(c, (hipError_t)e, "pil resize");
+    if (se != hipSuccess) return hip_fail(c, se, "pil resize sync");
+    return HAVC_OK;
+}
+
+extern "C" {
+
+int havc_pil_resize(havc_ctx* c, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, int resample) {
+    if (!c || !src || !dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || (resample != 2 && resample != 3))
+        return fail(c, HAVC_E_INVALID, "pil_resize: bad args (resample must be 2 = BILINEAR or 3 = BICUBIC)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    int rc;
+    const size_t sb = (size_t)sw * sh * 3, tb = (size_t)sh * dw * 3, db = (size_t)dw * dh * 3;
+    const uint8_t* d_src;
+    uint8_t* d_dst;
+    bool host;
+    if ((rc = stage_in(c, SCR_IN, src, sb, &d_src)) || (rc = ensure_scratch(c, SCR_PIL_ROWS, tb)) || (rc = stage_out_ptr(c, SCR_OUT, dst, db, &d_dst, &host))) return rc;
+    if ((rc = pil_resize_dev(c, d_src, sw, sh, (uint8_t*)c->scratch[SCR_PIL_ROWS], d_dst, dw, dh, 1, resample))) return rc;
+    return stage_out(c, dst, d_dst, db, host);
+}
+
+int havc_spline64_resize(havc_ctx* c, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, const uint8_t* luma_from) {
+    return havc_spline64_resize_n(c, src, sw, sh, dst, dw, dh, luma_from, 1);
+}
+
+int havc_spline64_resize_n(havc_ctx* c, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, const uint8_t* luma_from, int n_frames) {
+    if (!c || !src || !dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || n_frames < 1) return fail(c, HAVC_E_INVALID, "spline64_resize: bad args");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    const size_t sb = (size_t)sw * sh * 3 * n_frames, db = (size_t)dw * dh * 3 * n_frames;
+    int rc;
+    const uint8_t *d_src, *d_luma = nullptr;
+    uint8_t* d_dst;
+    bool host;
+    if ((rc = stage_in(c, SCR_IN, src, sb, &d_src)) || (rc = stage_out_ptr(c, SCR_OUT, dst, db, &d_dst, &host)) ||
+        (luma_from && (rc = stage_in(c, SCR_IN3, luma_from, db, &d_luma)))) return rc;
+    if (sw == dw && sh == dh && !luma_from) {
+        HIP_TRY(c, hipMemcpyAsync(d_dst, d_src, sb, hipMemcpyDeviceToDevice, c->stream));
+    } else if ((rc = resize_rgb8(c, d_src, sw, sh, d_dst, dw, dh, n_frames, d_luma)))
+        return rc;
+    return stage_out(c, dst, d_dst, db, host);
+}
+
+}  // extern "C"

@@ -1,0 +1,286 @@
+// What the units of the libhavc_mi355.so runtime (rt_*.cpp) share: the context / weights / net structs, error and set-up helpers, the scratch pool and
+// its slot names, operand staging, and the few functions that cross units.  Not installed; include/havc_mi355.h is the public interface.
+#pragma once
+#include "../../include/havc_mi355.h"
+#include "kernels.h"
+
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+
+// Set-up is serialised process-wide (rt_context.cpp says what counts as set-up and why).
+extern std::recursive_mutex g_setup_mu;      // recursive: the autotuner's trial launches may regrow the split-K workspace (ensure_scratch)
+// HAVC_SETUP_MUTEX=0 turns the lock into a no-op (tools/setup_stress.py bisects with it; never a production setting)
+struct SetupLock {
+    bool on;
+    SetupLock() {
+        static const bool enabled = [] { const char* e = getenv("HAVC_SETUP_MUTEX"); return e ? atoi(e) != 0 : true; }();
+        on = enabled;
+        if (on) g_setup_mu.lock();
+    }
+    ~SetupLock() { if (on) g_setup_mu.unlock(); }
+    SetupLock(const SetupLock&) = delete;
+    SetupLock& operator=(const SetupLock&) = delete;
+};
+
+extern thread_local std::string g_create_error;            // havc_last_error(NULL): why the last havc_create of this thread failed
+
+// HAVC_STREAM_JITTER / havc_debug_stream_jitter (rt_context.cpp): off, one predictable branch, unless switched on
+struct JitterState {
+    bool on = false;
+    unsigned max_us = 300;
+    std::atomic<uint64_t> rng{0x9E3779B97F4A7C15ull};
+    JitterState() {
+        const char* e = getenv("HAVC_STREAM_JITTER");
+        if (e && *e && atoll(e) != 0) {
+            on = true;
+            rng = 0x9E3779B97F4A7C15ull * (uint64_t)(atoll(e) + 1);
+            if (const char* m = getenv("HAVC_STREAM_JITTER_US")) max_us = (unsigned)std::max(1, atoi(m));
+        }
+    }
+};
+extern JitterState g_jitter;
+void stream_jitter_delay(hipStream_t st);
+// one call = at most one delay kernel on `st` (two calls in three launch nothing: the un-delayed interleavings stay in the mix)
+inline void stream_jitter(hipStream_t st) {
+    if (!g_jitter.on) return;
+    stream_jitter_delay(st);
+}
+
+struct ResizeTable {
+    int taps = 0;
+    int* d_start = nullptr;
+    float* d_w = nullptr;
+};
+
+// ---- the scratch pool: havc_ctx::scratch[slot], grow-only (ensure_scratch), reused every call.  This enum is the one record of who owns which slot. ----
+// Enumerators that share a value sit on adjacent lines.  Sharing is safe because every user of a shared slot holds c->mu for its whole call and leaves
+// nothing behind in it.  The exception are SCR_BANK_*: they carry state ACROSS calls and therefore share with nobody.
+enum ScratchSlot {
+    // 0-5: host operands on their way to the device and results on their way back (stage_in / stage_out_ptr; device operands are used in place)
+    SCR_IN = 0,                        // first operand: the image / clip of a filter, the frames entering a model; fp32 ColorMNet ops: mk / q / L plane
+    SCR_IN2 = 1,                       // second operand: image b of a two-input filter; ColorMNet: qk / k / ab
+    SCR_VIDEO = SCR_IN2,               //   DeOldify drivers: raw colour of the video model
+    SCR_PIL_ROWS = SCR_IN2,            //   u8 row pass of a Pillow resize (havc_pil_resize, the Zhang / DDColor squash to S x S)
+    SCR_OUT = 2,                       // result of a filter / resize / ColorMNet op on its way to the host; the host tiles of havc_tile_slice
+    SCR_SECOND = SCR_OUT,              //   DeOldify drivers: raw colour of the second (stable / artistic) model
+    SCR_SQUARE = SCR_OUT,              //   Zhang / DDColor: the frames squashed to the net's S x S input
+    SCR_IN3 = 3,                       // third operand: luma_from of the Spline64 resize; ColorMNet: mv / v
+    SCR_RESULT = SCR_IN3,              //   model drivers: the finished frames (blend / post-process output) on their way to the host
+    SCR_IN4 = 4,                       // ColorMNet: ms (shrinkage) / rel_w
+    SCR_PLANES = SCR_IN4,              //   planar entry points: the three planes of a frame, in and (u8) out
+    SCR_IN5 = 5,                       // ColorMNet: qe (selection) / rel_b
+    SCR_PLANES_OUT = SCR_IN5,          //   havc_ddcolor_frame_planar_f: the float / half planes on their way out
+    SCR_SMALL = 6,                     // small results and tables: luma sums, a 256-byte LUT, scene records, the equalisation workspace, a usage vector
+    SCR_RESIZE_ROWS = 7,               // fp32 rows between the two passes of the Spline64 resize
+    // 8-11: the pipelined host clip (havc_colorize_clip_host), double-buffered by batch parity; the ONE-SHOT ColorMNet reads reuse them
+    SCR_CLIP_SRC = 8,                  // 8, 9: source batches, SCR_CLIP_SRC + (batch & 1)
+    SCR_SIM = SCR_CLIP_SRC,            //   one-shot read: similarity map [B][N][HW]; havc_local_attention: the attention map
+    SCR_TOPK_IDX = SCR_CLIP_SRC + 1,   //   one-shot read: top-k indices (and, behind them, the level-1 survivors of the two-level selection)
+    SCR_CLIP_DST = 10,                 // 10, 11: result batches, SCR_CLIP_DST + (batch & 1)
+    SCR_TOPK_W = SCR_CLIP_DST,         //   one-shot read: top-k weights (and level-1 survivors)
+    SCR_USAGE_ACC = SCR_CLIP_DST + 1,  //   one-shot read: usage accumulators
+    // 12, 13: split-K partial sums, one workspace per stream: the two generators of a stable / artistic render run side by side
+    SCR_SPLITK_MAIN = 12,              // launches on havc_ctx::stream
+    SCR_SPLITK_SIDE = 13,              // launches on havc_ctx::stream2
+    // 14-17: the BANKED memory read of the ColorMNet frame loop (havc_memory_read_banked / _reserve, usage_update_locked).  Its own slots, because a read
+    // that runs ahead (havc_cmn_side_begin) leaves its top-k lists here until its frame is stepped (havc_cmn_side_wait): between a read-ahead and its
+    // step NO other entry point may touch them.
+    SCR_BANK_SIM = 14,                 // similarity map [N][HW]
+    SCR_BANK_IDX = 15,                 // top-k indices (+ level-1 survivors)
+    SCR_BANK_W = 16,                   // top-k weights (+ level-1 survivors)
+    SCR_BANK_ACC = 17,                 // usage accumulators, kept at zero between reads (havc_ctx::acc_clean_sz)
+    SCR_COUNT = 18
+};
+
+struct havc_ctx {
+    int dev = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t stream2 = nullptr;        // the second generator of a stable/artistic render runs here, concurrently
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_main_done = nullptr, ev_side = nullptr, ev_mark = nullptr;
+    bool marked = false;                  // havc_cmn_side_mark recorded ev_mark: the next side section starts behind THAT point of the main stream
+    bool stream_exported = false;         // havc_get_stream handed a stream handle out: the streams may not be re-created any more (havc_ctx_set_stream_*)
+    bool side = false;                    // between havc_cmn_side_begin / _end: the ColorMNet read (short-term attention, memory read, join) is enqueued on stream2
+    size_t acc_clean_sz = 0;              // SCR_BANK_ACC holds zeros over this many bytes (0: unknown -> cleared before use)
+    struct { float* use = nullptr; float* life = nullptr; int from = 0, N = 0, HW = 0, top_k = 0; } side_usage;   // its usage update, owed until havc_cmn_side_wait
+    hipStream_t cur = nullptr;            // stream the plan executor launches on (stream or stream2)
+    bool two_streams = true;              // HAVC_TWO_STREAMS=0 serialises the two generators (A/B measurements)
+    bool range_check = false;             // HAVC_RANGE_CHECK / havc_range_check_enable: scan every op's destination for inf / NaN / abs-max
+    uint64_t nt_store_bytes = 0;          // conv outputs at least this large are written with non-temporal stores (0 = never); HAVC_NT_STORE_MB
+    uint64_t desc_limit = 0xE0000000ull;  // bytes one conv launch may address per operand (32-bit buffer descriptors);
+                                          // HAVC_DESC_LIMIT_BYTES lowers it so tests reach the frame-chunking path at small sizes
+    std::mutex mu;
+    std::string err;
+    havc_stats stats{};
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    void* scratch[SCR_COUNT] = {nullptr};  // grow-only scratch, indexed by ScratchSlot: allocated once, reused every call
+    size_t scratch_sz[SCR_COUNT] = {0};
+    hipStream_t stream_h2d = nullptr, stream_d2h = nullptr;      // copy streams of havc_colorize_clip_host (created on first use)
+    hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_down[2] = {nullptr, nullptr};
+    std::map<std::pair<int, int>, ResizeTable> resize_tables;
+    // per-tag timing
+    int timed_tag = -1;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> tag_events;
+    size_t tag_used = 0;
+    double tag_ms = 0;
+    int64_t tag_launches = 0;
+};
+
+struct havc_weights {
+    havc_ctx* ctx;
+    uint8_t* d_blob;
+    size_t nbytes;
+};
+
+struct havc_net {
+    havc_ctx* ctx;
+    havc_weights* w;
+    std::vector<havc_op> ops;
+    std::vector<havc_buf> bufdesc;
+    std::vector<void*> bufs;
+    int in_buf, out_buf, S, max_batch;
+    int tail_first = -1;                  // index of the first op tagged 1 (exclusive tail), -1 if none
+    int2* d_ktab = nullptr;               // all conv K tables, one allocation
+    std::vector<int64_t> ktab_off;        // per op: element offset into d_ktab, -1 for non-conv ops
+    const void* in_override = nullptr;
+    void* out_override = nullptr;
+    unsigned* d_range = nullptr;          // range check: per op {abs-max bits, -, non-finite count (64 bit)}
+    bool range_ready = false;             // buffers were zero-filled at creation (never-written padding cannot trip the scan)
+    std::vector<float> range_absmax;
+    std::vector<int64_t> range_bad;
+    std::vector<void*> bound;             // havc_net_bind: caller-owned device memory standing in for a buffer (nullptr = own allocation)
+    double flops_per_frame = 0;
+};
+
+inline int fail(havc_ctx* c, int code, const std::string& msg) {
+    if (c) c->err = msg; else g_create_error = msg;
+    return code;
+}
+
+inline int hip_fail(havc_ctx* c, hipError_t e, const char* what) {
+    std::string m = std::string(what) + ": " + hipGetErrorString(e);
+    (void)hipGetLastError();
+    return fail(c, e == hipErrorOutOfMemory ? HAVC_E_OOM : HAVC_E_HIP, m);
+}
+
+#define HIP_TRY(ctx, expr)                                         \
+    do {                                                           \
+        hipError_t _e = (expr);                                    \
+        if (_e != hipSuccess) return hip_fail((ctx), _e, #expr);   \
+    } while (0)
+
+// Both streams idle: required before anything either of them may still touch is freed or re-allocated.
+inline hipError_t sync_streams(havc_ctx* c) {
+    hipError_t a = hipStreamSynchronize(c->stream);
+    hipError_t b = c->stream2 ? hipStreamSynchronize(c->stream2) : hipSuccess;
+    return a != hipSuccess ? a : b;
+}
+
+int ensure_scratch(havc_ctx* c, int slot, size_t nbytes);                                   // rt_context.cpp
+
+// ---- functions that cross units ----
+int run_ops_locked(havc_net* n, int first, int count, int batch);                           // rt_net.cpp
+int net_run_rgb8_locked(havc_net* n, const uint8_t* d_in, uint8_t* d_out, int batch, hipStream_t on = nullptr);
+int resize_rgb8(havc_ctx* c, const uint8_t* d_src, int sw, int sh, uint8_t* d_dst, int dw, int dh, int n, const uint8_t* d_orig);   // rt_resize.cpp
+int pil_resize_dev(havc_ctx* c, const uint8_t* d_src, int sw, int sh, uint8_t* d_tmp, uint8_t* d_dst, int dw, int dh, int n, int resample);
+
+inline void* bufptr(havc_net* n, int id) {
+    if (id == n->in_buf && n->in_override) return const_cast<void*>(n->in_override);
+    if (id == n->out_buf && n->out_override) return n->out_override;
+    if (!n->bound.empty() && n->bound[id]) return n->bound[id];
+    return n->bufs[id];
+}
+
+template <typename T>
+inline const T* wptr(havc_net* n, int64_t off) {
+    return off < 0 ? nullptr : reinterpret_cast<const T*>(n->w->d_blob + off);
+}
+
+struct Timer {
+    havc_ctx* c;
+    explicit Timer(havc_ctx* ctx) : c(ctx) { (void)hipEventRecord(c->ev0, c->stream); }
+    int finish() {
+        HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+        HIP_TRY(c, hipEventSynchronize(c->ev1));
+        float ms = 0;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        c->stats.last_ms = ms;
+        c->stats.total_ms += ms;
+        return HAVC_OK;
+    }
+};
+
+// ---- pointer-agnostic operands ---------------------------------------------------------------------------------------
+// Every frame / filter entry point accepts HOST or DEVICE pointers for its image operands (unified addressing tells them apart).
+// Host operands are staged through the ctx scratch buffers and the call blocks until the result is back in host memory; device
+// operands (havc_dev_alloc, or any hipMalloc of this device) are used in place, nothing is copied and the call only ENQUEUES
+// work on the ctx stream (havc_synchronize / a later host-output call / havc_dev_download order against it).  This is what
+// lets a whole HAVC merge graph run without leaving HBM (vsdeoldify_amd/device.py).
+inline bool is_device_ptr(const void* p) {
+    if (!p) return false;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return at.type == hipMemoryTypeDevice;
+}
+
+inline int stage_in(havc_ctx* c, int slot, const void* p, size_t nbytes, const uint8_t** d) {
+    if (is_device_ptr(p)) { *d = (const uint8_t*)p; return HAVC_OK; }
+    int rc = ensure_scratch(c, slot, nbytes);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->scratch[slot], p, nbytes, hipMemcpyHostToDevice, c->stream));
+    *d = (const uint8_t*)c->scratch[slot];
+    return HAVC_OK;
+}
+
+inline int stage_in_f(havc_ctx* c, int slot, const void* p, size_t nbytes, const float** d) {
+    const uint8_t* q = nullptr;
+    int rc = stage_in(c, slot, p, nbytes, &q);
+    *d = reinterpret_cast<const float*>(q);
+    return rc;
+}
+
+inline int stage_out_ptr(havc_ctx* c, int slot, void* p, size_t nbytes, uint8_t** d, bool* host) {
+    *host = !is_device_ptr(p);
+    if (!*host) { *d = (uint8_t*)p; return HAVC_OK; }
+    int rc = ensure_scratch(c, slot, nbytes);
+    if (rc) return rc;
+    *d = (uint8_t*)c->scratch[slot];
+    return HAVC_OK;
+}
+
+inline int stage_out(havc_ctx* c, void* p, const uint8_t* d, size_t nbytes, bool host) {
+    if (!host) return HAVC_OK;
+    HIP_TRY(c, hipMemcpyAsync(p, d, nbytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HAVC_OK;
+}
+
+// two-input (b may be NULL) / one-output per-pixel filter: stage, launch, hand back
+template <typename Launch, typename Pre>
+inline int run_filter(havc_ctx* c, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t nbytes, const char* what, Launch launch, Pre pre) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    const uint8_t *da = nullptr, *db = nullptr;
+    uint8_t* dout = nullptr;
+    bool host = false;
+    int rc;
+    if ((rc = pre())) return rc;
+    if ((rc = stage_in(c, SCR_IN, a, nbytes, &da))) return rc;
+    if (b && (rc = stage_in(c, SCR_IN2, b, nbytes, &db))) return rc;
+    if ((rc = stage_out_ptr(c, SCR_OUT, out, nbytes, &dout, &host))) return rc;
+    const int e = launch(da, db, dout);
+    c->stats.launches++;
+    if (e) return hip_fail(c, (hipError_t)e, what);
+    return stage_out(c, out, dout, nbytes, host);
+}
+template <typename Launch>
+inline int run_filter(havc_ctx* c, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t nbytes, const char* what, Launch launch) {
+    return run_filter(c, a, b, out, nbytes, what, launch, []() { return HAVC_OK; });
+}

@@ -259,7 +259,7 @@ class HAVCFrameColorizer:
         if self._side_by_side() and is_device(sq):
             # The two models side by side on two contexts, DDColor driven from a second thread -- from the first clip on: building the models,
             # their nets and the tile autotuning from two host threads at once is serialised INSIDE the library (the set-up mutex of
-            # csrc/havc_runtime.cpp; the reference's glue builds models from whichever worker thread asks first, vsslib/vsmodels.py:196-233).
+            # csrc/rt_context.cpp; the reference's glue builds models from whichever worker thread asks first, vsslib/vsmodels.py:196-233).
             import concurrent.futures
             if self._pool is None:
                 self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
