@@ -542,6 +542,12 @@ int havc_spline64_resize(havc_ctx* ctx, const uint8_t* src, int sw, int sh, uint
 /* n_frames tightly packed frames per operand in one call (device-resident clips) */
 int havc_spline64_resize_n(havc_ctx* ctx, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, const uint8_t* luma_from,
                            int n_frames);
+/* What the horizontal pass of havc_spline64_resize[_n] does for rows of sw pixels resampled to dw, n_rows = n_frames * sh of them in one call: *h_taps = taps
+ * per output, *h_variant = 0 for the one-block-per-row kernel, otherwise the tap bound (9 / 17 / 29 / 32 / 48) of the batched kernel instance that runs (either
+ * pointer may be NULL).  Returns the bytes of LDS the batched kernel reserves for a 256-column tile's source span (it is chosen only up to 4096), or
+ * HAVC_E_INVALID.  Host arithmetic only: no context, no GPU call.  The launcher takes its decision from the same function, so tests can pin which kernel a
+ * shape exercises. */
+int havc_resize_plan(int sw, int dw, int n_rows, int* h_taps, int* h_variant);
 int havc_dev_alloc(havc_ctx* ctx, size_t nbytes, void** out);
 int havc_dev_free(havc_ctx* ctx, void* p);
 int havc_dev_upload(havc_ctx* ctx, void* d_dst, const void* h_src, size_t nbytes);

@@ -42,7 +42,7 @@ def test_pil_resize_restatement_bit_exact():
     from PIL import Image
     r = np.random.default_rng(0)
     for (h, w), (oh, ow) in (((54, 96), (64, 64)), ((64, 64), (54, 96)), ((135, 240), (256, 256)), ((100, 100), (256, 256)),
-                             ((256, 256), (256, 256)), ((33, 200), (256, 256))):
+                             ((256, 256), (256, 256)), ((33, 200), (256, 256)), ((64, 96), (64, 48)), ((64, 96), (40, 96))):      # the last two: one axis only
         a = r.integers(0, 256, (h, w, 3), dtype=np.uint8)
         for rs in (2, 3):
             ref = np.asarray(Image.fromarray(a).resize((ow, oh), resample=rs))
@@ -81,7 +81,7 @@ def test_gpu_pil_resize_bit_exact(ctx):
     from vsdeoldify_amd.colorization import pil_resize_np
     r = np.random.default_rng(3)
     for (h, w), (oh, ow) in (((54, 96), (64, 64)), ((64, 64), (54, 96)), ((270, 480), (256, 256)), ((100, 60), (256, 256)),
-                             ((256, 256), (256, 256)), ((560, 560), (1080, 1920))):
+                             ((256, 256), (256, 256)), ((560, 560), (1080, 1920)), ((64, 96), (64, 48)), ((64, 96), (40, 96))):   # the last two: one axis only
         a = r.integers(0, 256, (h, w, 3), dtype=np.uint8)
         for rs in (2, 3):
             ref = np.asarray(Image.fromarray(a).resize((ow, oh), resample=rs))

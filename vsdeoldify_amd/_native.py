@@ -161,6 +161,7 @@ SYMBOLS = [
     ("havc_colorize_clip", _I, [_P, _P, _P, _F, _P, _P, _I, _I, _I]),
     ("havc_spline64_resize", _I, [_P, _P, _I, _I, _P, _I, _I, _P]),
     ("havc_spline64_resize_n", _I, [_P, _P, _I, _I, _P, _I, _I, _P, _I]),
+    ("havc_resize_plan", _I, [_I, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
     ("havc_colorize_clip_host", _I, [_P, _P, _P, _F, _P, _P, _I, _I, _I]),
     ("havc_host_alloc", _I, [_P, _SZ, C.POINTER(_P)]),
     ("havc_host_free", _I, [_P, _P]),

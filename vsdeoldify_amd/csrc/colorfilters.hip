@@ -360,40 +360,47 @@ __global__ void __launch_bounds__(256) resize_v4_kernel(const float* __restrict_
     }
 }
 
+// Which horizontal pass launch_resize_passes runs: 0 = resize_h_kernel (one block per row), otherwise the TMAX of the resize_h_rows_kernel instance.
+// The batched kernel needs taps <= 48, a tile's staged source span within 4 KiB (four prefetched dwords per thread) and enough blocks to fill the chip.
+// *span_lds (optional): the LDS bytes reserved for the span, whichever kernel is chosen.  Pure host arithmetic: havc_resize_plan reports it to the tests.
+int resize_h_variant(int sw, int dw, int h_taps, int64_t rows, int* span_lds) {
+    // source span of a 256-column tile: 256 outputs step (sw / dw) source pixels each, plus the taps
+    const size_t span_px = (size_t)((255.0 * sw) / dw) + h_taps + 4;
+    const size_t lds_t = (span_px * 3 + 8 + 15) & ~(size_t)15;
+    if (span_lds) *span_lds = lds_t < 0x7fffffff ? (int)lds_t : 0x7fffffff;
+    if (h_taps > 48 || lds_t > 4096) return 0;          // (spans up to 4 KiB: four prefetched dwords per thread)
+    // 16 rows per block amortise the per-thread tap loads; a single frame (ColorMNet: one squash per call) does not fill the chip that way and
+    // keeps the one-block-per-row pass (measured: c5 -0.7 % with one row per block here)
+    const int64_t chunks = (rows + RESIZE_H_ROWS_PER_BLOCK - 1) / RESIZE_H_ROWS_PER_BLOCK, xt = (dw + 255) / 256;
+    if (chunks * xt < 2048 || chunks > 65535) return 0;
+    return h_taps <= 9 ? 9 : h_taps <= 17 ? 17 : h_taps <= 29 ? 29 : h_taps <= 32 ? 32 : 48;
+}
+
 int launch_resize_passes(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, int n_frames, float* tmp,
                          const int* h_start, const float* h_w, int h_taps, const int* v_start, const float* v_w,
                          int v_taps, const uint8_t* orig, hipStream_t s) {
     const int64_t rows = (int64_t)n_frames * sh;
-    // source span of a 256-column tile: 256 outputs step (sw / dw) source pixels each, plus the taps
-    const size_t span_px = (size_t)((255.0 * sw) / dw) + h_taps + 4;
-    const size_t lds_t = (span_px * 3 + 8 + 15) & ~(size_t)15;
-    if (h_taps <= 48 && lds_t <= 4096) {                // (spans up to 4 KiB: four prefetched dwords per thread)
-        const int xt = (dw + 255) / 256;
-        // 16 rows per block amortise the per-thread tap loads; a single frame (ColorMNet: one squash per call) does not fill the chip that way and
-        // keeps the one-block-per-row pass (measured: c5 -0.7 % with one row per block here)
-        const int rpb = 16;
+    int span_lds = 0;
+    const int variant = resize_h_variant(sw, dw, h_taps, rows, &span_lds);
+    if (variant) {
+        const int xt = (dw + 255) / 256, rpb = RESIZE_H_ROWS_PER_BLOCK;
         const int64_t chunks = (rows + rpb - 1) / rpb;
-        if (chunks * xt >= 2048 && chunks <= 65535) {
-            const int vec_out = ((dw & 3) == 0 && (reinterpret_cast<uintptr_t>(tmp) & 15) == 0) ? 1 : 0;
-            const int out_off = (int)lds_t;                                    // [256][3] floats behind the staged span
-            const size_t lds_all = lds_t + 256 * 3 * sizeof(float);
+        const int vec_out = ((dw & 3) == 0 && (reinterpret_cast<uintptr_t>(tmp) & 15) == 0) ? 1 : 0;
+        const int out_off = span_lds;                                      // [256][3] floats behind the staged span
+        const size_t lds_all = (size_t)span_lds + 256 * 3 * sizeof(float);
 #define HAVC_RH(T) hipLaunchKernelGGL(resize_h_rows_kernel<T>, dim3(xt, (unsigned)chunks), dim3(256), lds_all, s, src, tmp, h_start, h_w, h_taps, sw, dw, rows, rpb, out_off, vec_out)
-            if (h_taps <= 9) HAVC_RH(9);              // every up-sampling pass
-            else if (h_taps <= 17) HAVC_RH(17);
-            else if (h_taps <= 29) HAVC_RH(29);       // 1920 -> 560 (c2), 1920 -> 512 is 31 taps
-            else if (h_taps <= 32) HAVC_RH(32);
-            else HAVC_RH(48);                         // 1920 -> 384 (c4): 41 taps
+        if (variant == 9) HAVC_RH(9);                 // every up-sampling pass
+        else if (variant == 17) HAVC_RH(17);
+        else if (variant == 29) HAVC_RH(29);          // 1920 -> 560 (c2), 1920 -> 512 is 31 taps
+        else if (variant == 32) HAVC_RH(32);
+        else HAVC_RH(48);                             // 1920 -> 384 (c4): 41 taps
 #undef HAVC_RH
-            goto vertical;
-        }
-    }
-    {
+    } else {
         const size_t lds = (size_t)(sw * 3 + 8 + 15) & ~(size_t)15;
         if (lds > 64 * 1024) return (int)hipErrorInvalidValue;            // rows beyond 21 800 pixels: not a video frame
         hipLaunchKernelGGL(resize_h_kernel, dim3((unsigned)(rows < 65535 * 16 ? rows : 65535 * 16)), dim3(256), lds, s, src, tmp, h_start, h_w,
                            h_taps, sw, dw, rows);
     }
-vertical:
     const int groups = (dh + VR - 1) / VR;
     const bool quad = (dw & 3) == 0 && ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(orig)) & 3) == 0 &&
                       (reinterpret_cast<uintptr_t>(tmp) & 15) == 0;

@@ -211,6 +211,10 @@ int launch_restore_color_gradient(const uint8_t* color, const uint8_t* gray, uin
 int launch_resize_passes(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, int n_frames, float* tmp,
                          const int* h_start, const float* h_w, int h_taps, const int* v_start, const float* v_w,
                          int v_taps, const uint8_t* orig, hipStream_t s);
+// the horizontal kernel launch_resize_passes picks for a shape (host arithmetic only): 0 = resize_h_kernel, else the TMAX of resize_h_rows_kernel<TMAX>;
+// *span_lds (optional) = the LDS bytes reserved for a 256-column tile's source span
+constexpr int RESIZE_H_ROWS_PER_BLOCK = 16;
+int resize_h_variant(int sw, int dw, int h_taps, int64_t rows, int* span_lds = nullptr);
 
 // ---- ColorMNet memory kernels (colormnet.hip) ----
 int launch_mem_similarity(const float* mk, const float* ms, const float* qk, const float* qe, float* sim, int B, int CK, int N, int HW, hipStream_t s,

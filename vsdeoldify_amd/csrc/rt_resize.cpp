@@ -13,14 +13,18 @@ double spline64(double x) {
     return 0.0;
 }
 
+// kernel stretch for anti-aliasing when downscaling, and the taps per output of a src -> dst pass (the table below and havc_resize_plan)
+double resize_fscale(int src, int dst) { const double scale = (double)dst / (double)src; return scale < 1.0 ? scale : 1.0; }
+int resize_taps(int src, int dst) { return (int)std::ceil(2.0 * (4.0 / resize_fscale(src, dst))) + 1; }
+
 int get_resize_table(havc_ctx* c, int src, int dst, ResizeTable** out) {
     auto key = std::make_pair(src, dst);
     auto it = c->resize_tables.find(key);
     if (it != c->resize_tables.end()) { *out = &it->second; return HAVC_OK; }
     const double scale = (double)dst / (double)src;
-    const double fscale = scale < 1.0 ? scale : 1.0;       // kernel stretch for anti-aliasing
+    const double fscale = resize_fscale(src, dst);
     const double support = 4.0 / fscale;
-    const int taps = (int)std::ceil(2.0 * support) + 1;
+    const int taps = resize_taps(src, dst);
     std::vector<int> start(dst);
     std::vector<float> w((size_t)dst * taps);
     for (int i = 0; i < dst; ++i) {
@@ -144,6 +148,16 @@ int havc_pil_resize(havc_ctx* c, const uint8_t* src, int sw, int sh, uint8_t* ds
     if ((rc = stage_in(c, SCR_IN, src, sb, &d_src)) || (rc = ensure_scratch(c, SCR_PIL_ROWS, tb)) || (rc = stage_out_ptr(c, SCR_OUT, dst, db, &d_dst, &host))) return rc;
     if ((rc = pil_resize_dev(c, d_src, sw, sh, (uint8_t*)c->scratch[SCR_PIL_ROWS], d_dst, dw, dh, 1, resample))) return rc;
     return stage_out(c, dst, d_dst, db, host);
+}
+
+int havc_resize_plan(int sw, int dw, int n_rows, int* h_taps, int* h_variant) {
+    if (sw <= 0 || dw <= 0 || n_rows <= 0) return HAVC_E_INVALID;
+    const int taps = resize_taps(sw, dw);
+    int span_lds = 0;
+    const int variant = resize_h_variant(sw, dw, taps, n_rows, &span_lds);
+    if (h_taps) *h_taps = taps;
+    if (h_variant) *h_variant = variant;
+    return span_lds;
 }
 
 int havc_spline64_resize(havc_ctx* c, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, const uint8_t* luma_from) {
