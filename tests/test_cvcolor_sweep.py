@@ -2,7 +2,7 @@
 ALL inputs against the float definitions OpenCV documents for the same codes.  Every byte of the headline output passes through
 cvtColor(RGB2YUV / YUV2RGB) twice (deoldify/filters.py:100-110 at the net size, vsslib/vsfilters.py:863-899 at 1080p); the HSV pair carries
 image_chroma_tweak / adjust_hue_range / restore_color_gradient (vsslib/restcolor.py:98-350).  The library's kernels are bit-exact against
-oracle/cvcolor.py (tests/test_filters2.py, test_tweaks.py), so a bound on cvcolor-vs-definition is a bound on how far library AND oracle could be
+oracle/cvcolor.py over the same 2^24 inputs (tests/test_gpu_colour_sweep.py), so a bound on cvcolor-vs-definition is a bound on how far library AND oracle could be
 from a real cv2 build: the fixed-point tables can differ from the real-valued formula by rounding only.
 Float definitions (OpenCV docs, "Color conversions"):  Y = 0.299 R + 0.587 G + 0.114 B, U = 0.492 (B - Y) + 128, V = 0.877 (R - Y) + 128;
 R = Y + 1.140 V', G = Y - 0.395 U' - 0.581 V', B = Y + 2.032 U';  V = max, S = 255 (V - min) / V, H = 30 (G - B) / (V - min) [+60 / +120 per sextant],

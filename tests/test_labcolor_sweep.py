@@ -1,7 +1,7 @@
 """CPU: bound the UNPINNED restatement of scikit-image's rgb2lab / lab2rgb (oracle/zhang.py; skimage is absent from the build container) by sweeping
 ALL 2^24 sRGB inputs against the float64 DEFINITION of the same transform (the cv2 analogue is tests/test_cvcolor_sweep.py).
 Every byte of a Zhang (colorizers/util.py:25-55), DDColor and ColorMNet (colormnet_utils.py:185-197) frame passes through this pair: L of the source
-in, Lab -> RGB out.  The library's kernels (csrc/zhang.hip) are checked against oracle/zhang.py on the GPU (tests/test_zhang.py), so a bound on
+in, Lab -> RGB out.  The library's kernels (csrc/zhang.hip) are checked against oracle/zhang.py on the GPU over the same 2^24 inputs, bit for bit up to the derived 1e-6 share / 1e-9 window stated there (tests/test_gpu_colour_sweep.py), so a bound on
 oracle-vs-definition is a bound on how far library AND oracle could be from a real skimage build: skimage hard-codes ROUNDED constants (the
 0.412453 ... matrix, 0.008856, 7.787, the D65 white 0.95047 / 1.08883), the definition below derives them from first principles.
 
