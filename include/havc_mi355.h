@@ -120,6 +120,24 @@ enum havc_op_type {
     HAVC_OP_DWCONV7_LN = 17,    /* DWCONV7 followed by LAYERNORM of its result, one kernel (ConvNeXt block head): fields of both
                                 ops (w_off / bias_off / Kc; scale_off gamma, shift_off beta, f0 eps); Ci = 64, 192, 384, 768 or 1536.
                                 The norm reads the fp32 conv result (the two-op form rounds it to fp16 in between)      */
+    /* ---- DeepRemaster colour network (remaster/model/remasternet.py NetworkC; csrc/remaster.hip).  A plan of this model runs with batch = T frames
+       of one clip window: the batch entries of a buffer are the frames of the 5-D tensor, in order. ---- */
+    HAVC_OP_SRCREF_ATTN = 29,   /* SourceReferenceAttention (remasternet.py:31-77), flash form: out = f0 * softmax_k(q . k) v + x, no 1 / sqrt(d).  src / dst =
+                                source x and out views (Hi x Wi tokens per frame, Ci = value channels = 512); the queries are the tokens of ALL batch frames;
+                                src2 = query buffer (res_coff / res_cpitch, one frame per source frame); aux0 = key buffer: packed rows of kh = 64 channels,
+                                Ho * Wo rows per reference frame; aux1 = value buffer, TRANSPOSED per reference frame: [Ci][Kc] (Kc % 64 == 0, Kc >= Ho * Wo,
+                                zeros beyond the keys: the value conv's HAVC_F_OUT_TRANSPOSED store); kw = number of reference frames read from those two
+                                buffers (frame stride = the buffer's elems_per_frame; 0: the batch count, self-attention over the window).  The keys of a
+                                reference frame are walked in 64-key tiles, the tail masked; their order does not matter to the softmax                  */
+    HAVC_OP_TSTACK = 30,        /* temporal stacking for (3,3,3) convs: dst channel kt * Ci + c of frame t = src channel c of frame t + kt - 1 (kt = 0..2), zeros
+                                outside the batch: Conv3d(pad (1,1,1)) = the 3 x 3 conv over 3 Ci channels with weights [Co][kt][Ci][3][3]; Co = 3 Ci        */
+    HAVC_OP_ELU = 31,           /* y = x > 0 ? x : expm1(x) on a Ci-channel view, fp32 arithmetic (F.elu after conv + BatchNorm3d); dst may be src              */
+    HAVC_OP_PREP_REMASTER = 32, /* u8 RGB (buffer src, Hi x Wi) -> fp16 C8 view dst.  flags 0: the clip frames: OpenCV COLOR_RGB2GRAY
+                                ((4899 R + 9617 G + 1868 B + 8192) >> 14) / 255 - 0.4462414 in channel 0, ReplicationPad3d((1,1,1,1,0,0)): Ho = Hi + 2,
+                                Wo = Wi + 2.  flags 1: the reference stills: RGB / 255 - 0.48 in channels 0-2, Ho = Hi, Wo = Wi                              */
+    HAVC_OP_REMASTER_OUT = 33,  /* src = the last conv's view (channels 0-1, before the sigmoid), src2 = the u8 RGB frames PREP_REMASTER read -> dst u8 RGB:
+                                sigmoid, convertLAB2RGB (remaster_utils.py:29-33: L = gray / 255 * 100, clip(ab * 255 - 128, -100, 100) in fp32, skimage
+                                lab2rgb in fp64), trunc(x * 255).  aux0 >= 0: fp32 buffer that receives the sigmoid values [Hi * Wi][2] per frame            */
 };
 
 /* conv epilogue flags: v = acc + bias; RELU_PRE; v = v*scale+shift; v += residual; RELU_POST */

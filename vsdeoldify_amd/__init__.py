@@ -20,9 +20,13 @@ def __getattr__(name):
         from .ddcolor import DDColorRender
         return DDColorRender
     if name in ("HAVC_colorizer", "HAVC_merge", "HAVC_ddeoldify", "ddeoldify", "HAVC_stabilizer", "HAVCFrameColorizer", "HAVC_clip_slice",
-                "HAVC_clip_reconstruct", "ClipTiles", "tiled_preset_params", "HAVC_SceneDetect", "HAVC_deepex", "HAVC_auto_levels", "HAVC_bw_tune"):
+                "HAVC_clip_reconstruct", "ClipTiles", "tiled_preset_params", "HAVC_SceneDetect", "HAVC_deepex", "HAVC_auto_levels", "HAVC_bw_tune",
+                "HAVC_DeepRemaster"):
         from . import havc
         return getattr(havc, name)
+    if name == "RemasterRender":
+        from .remaster_render import RemasterRender
+        return RemasterRender
     if name in ("SceneInfo", "scene_flags"):
         from . import scdetect
         return getattr(scdetect, name)

@@ -257,6 +257,7 @@ void preload_ddcolor();
 void preload_colormnet();
 void preload_colormnet_net();
 void preload_precise();
+void preload_remaster();
 
 // ---- precise mode (precise.hip): the non-conv ops of the DeOldify generators on hi / lo fp16 pairs, fp32 arithmetic ----
 int launch_prep_rgb8_p(const uint8_t* rgb, half_t* y0, int y0_cpitch, int y0_coff, half_t* y1, int y1_cpitch, int y1_coff, int64_t npix, hipStream_t s);
@@ -329,3 +330,14 @@ int launch_planar_out(const half_t* x, int cp, int co, int64_t fs, float* y, int
 // the frame wrapper of ColorMNetRender (zhang.hip: skimage Lab formulas in fp64)
 int launch_cmn_rgb_to_lab(const uint8_t* rgb, float* lab, int64_t npix, hipStream_t s);
 int launch_cmn_lab_to_rgb(const float* l_plane, const float* ab, uint8_t* rgb, int64_t npix, hipStream_t s);
+
+// ---- DeepRemaster colour network (remaster.hip) ----
+bool srcref_attention_supported(int d, int dv);
+// q: [T][nq_frame][q_pitch] (64 channels at q_coff), k: [Tr][nk_frame][64], vT: [Tr][512][npitch]; x / out: the source and result views, T frames
+int launch_srcref_attention(const half_t* q, int q_pitch, int q_coff, int64_t q_fs, const half_t* k, int64_t k_fs, const half_t* vT, int npitch, int64_t v_fs,
+                            const half_t* x, int x_pitch, int x_coff, int64_t x_fs, half_t* out, int o_pitch, int o_coff, int64_t o_fs, int T, int nq_frame,
+                            int Tr, int nk_frame, float gamma, hipStream_t s);
+int launch_tstack(const half_t* x, half_t* y, int T, int64_t P, int C, int x_cp, int x_co, int64_t x_fs, int y_cp, int y_co, int64_t y_fs, hipStream_t s);
+int launch_elu(const half_t* x, half_t* y, int B, int64_t P, int C, int x_cp, int x_co, int64_t x_fs, int y_cp, int y_co, int64_t y_fs, hipStream_t s);
+int launch_prep_remaster(const uint8_t* rgb, half_t* y, int B, int Hi, int Wi, int Ho, int Wo, int refs, int y_cp, int y_co, int64_t y_fs, hipStream_t s);
+int launch_remaster_out(const half_t* ab, int ab_cp, int ab_co, int64_t ab_fs, const uint8_t* rgb_in, uint8_t* out, float* ab_out, int B, int64_t P, hipStream_t s);

@@ -1,0 +1,306 @@
+// DeepRemaster colour network (remaster/model/remasternet.py NetworkC): the ops the other models do not have.
+//   srcref_attention_kernel  SourceReferenceAttention in flash form (HAVC_OP_SRCREF_ATTN)
+//   tstack_kernel            frames t-1, t, t+1 side by side in the channel dimension: the (3,3,3) convs run as 3 x 3 convs over 3 Ci channels
+//   elu_kernel               F.elu after conv + BatchNorm3d
+//   prep_remaster_kernel     u8 RGB -> the network's gray input (replicate-padded) / the reference stills
+//   remaster_out_kernel      sigmoid + convertLAB2RGB + u8
+#include "kernels.h"
+
+#include <mutex>
+
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+typedef float float4v __attribute__((ext_vector_type(4)));
+
+static inline int grid_for(int64_t work, int per_block = 256) {
+    int64_t g = (work + per_block - 1) / per_block;
+    return (int)(g < 1 ? 1 : (g > 65535 * 16 ? 65535 * 16 : g));
+}
+
+// ---- source-reference attention ---------------------------------------------------------------------------------------------------------------------
+// Same operand roles and fragment conventions as self_attention_kernel (attention.hip): S^T = K Q^T and O^T = V^T P^T on v_mfma_f32_16x16x32_f16, so a
+// lane owns ONE query column and the online-softmax maximum / sum are in-lane reductions plus two shuffles.  What differs:
+//   * queries and keys are different token sets: N_q = batch frames x tokens per frame (source), N_k = reference frames x keys per frame, and the keys of a
+//     reference frame are a tile sequence of their own (tail masked), so a frame is a unit that can sit in any slot of the reference ring;
+//   * a block owns ALL 512 value channels of its 64 queries: O^T = 32 fragments x 4 fp32 = 128 accumulator registers per lane (the unified 512-register
+//     file of a 256-thread block at two blocks per CU leaves 256 per lane) -- S is computed once per key tile, not once per 128- or 256-wide slice;
+//   * LDS per block: K tile 64 keys x 64 ch = 8 KiB + V^T tile 512 x 64 keys = 64 KiB = 72 KiB (dynamic, opt-in); two blocks per CU = 144 of 160 KiB.
+namespace {
+
+struct SrAttnArgs {
+    const half_t* q; const half_t* k; const half_t* vT; const half_t* x; half_t* out;
+    int q_pitch, q_coff, x_pitch, x_coff, o_pitch, o_coff, npitch;
+    int64_t q_fs, k_fs, v_fs, x_fs, o_fs;      // frame strides, elements
+    int nq_frame, NQ, nk_frame, Tr;
+    float gamma;
+};
+
+__device__ __forceinline__ int swzr(int row) { return (4 - ((row >> 2) & 3)) & 3; }
+__device__ __forceinline__ int swzk(int row) { return (4 - ((row >> 3) & 3)) & 3; }
+
+constexpr int SR_D = 64, SR_DV = 512, SR_TF = SR_DV / 16;
+constexpr int SR_KS = SR_D / 32, SR_KCH = SR_D / 8;
+constexpr int SR_LDS_BYTES = (SR_KS * 64 * 32 + 2 * SR_DV * 32) * 2;
+
+__global__ void __launch_bounds__(256, 2) srcref_attention_kernel(const SrAttnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char sr_smem[];
+    half_t* Ks = reinterpret_cast<half_t*>(sr_smem);
+    half_t* Vs = Ks + SR_KS * 64 * 32;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lr = lane & 15, lg = lane >> 4;
+    const int q = blockIdx.x * 64 + wave * 16 + lr;
+    const bool q_ok = q < a.NQ;
+    const int qf_ = q_ok ? q / a.nq_frame : 0, qp = q_ok ? q - qf_ * a.nq_frame : 0;
+
+    half8 qf[SR_KS];
+#pragma unroll
+    for (int ks = 0; ks < SR_KS; ++ks) {
+        half8 v;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = (half_t)0.f;
+        if (q_ok) v = *reinterpret_cast<const half8*>(a.q + qf_ * a.q_fs + (int64_t)qp * a.q_pitch + a.q_coff + ks * 32 + lg * 8);
+        qf[ks] = v;
+    }
+
+    float4v o[SR_TF];
+#pragma unroll
+    for (int t = 0; t < SR_TF; ++t) o[t] = float4v{0.f, 0.f, 0.f, 0.f};
+    float m_run = -1e30f, l_run = 0.f;
+
+    for (int r = 0; r < a.Tr; ++r) {
+        const half_t* k_r = a.k + r * a.k_fs;
+        const half_t* v_r = a.vT + r * a.v_fs;
+        for (int kv0 = 0; kv0 < a.nk_frame; kv0 += 64) {
+            __syncthreads();
+            // ---- stage the K tile [KS][64 keys][32] (zeros past the frame's keys) and the V^T tile [2][512 dv][32 keys] (npitch % 64 == 0: in range) ----
+#pragma unroll
+            for (int it = 0; it < 64 * SR_KCH / 256; ++it) {
+                const int i = tid + it * 256;
+                const int key = i / SR_KCH, c = i % SR_KCH;
+                uint4 v = make_uint4(0, 0, 0, 0);
+                if (kv0 + key < a.nk_frame) v = *reinterpret_cast<const uint4*>(k_r + (int64_t)(kv0 + key) * SR_D + c * 8);
+                *reinterpret_cast<uint4*>(Ks + (((c >> 2) * 64 + key) * 4 + ((c & 3) ^ swzk(key))) * 8) = v;
+            }
+#pragma unroll 4                 // four 16-byte loads in flight per lane: the 128 accumulator registers leave no room for all sixteen
+            for (int it = 0; it < SR_DV * 8 / 256; ++it) {
+                const int i = tid + it * 256;
+                const int row = i >> 3, kc = i & 7;
+                const uint4 v = *reinterpret_cast<const uint4*>(v_r + (int64_t)row * a.npitch + kv0 + kc * 8);
+                *reinterpret_cast<uint4*>(Vs + (((kc >> 2) * SR_DV + row) * 4 + ((kc & 3) ^ swzr(row))) * 8) = v;
+            }
+            __syncthreads();
+
+            // ---- S^T[key][query]: fragment f = 2s+h covers keys 32s + (i>>2)*8 + h*4 + (i&3), i = row index ----
+            float4v sacc[4];
+#pragma unroll
+            for (int f = 0; f < 4; ++f) {
+                sacc[f] = float4v{0.f, 0.f, 0.f, 0.f};
+                const int key = 32 * (f >> 1) + (lr >> 2) * 8 + (f & 1) * 4 + (lr & 3);
+#pragma unroll
+                for (int ks = 0; ks < SR_KS; ++ks) {
+                    const half8 kf = *reinterpret_cast<const half8*>(Ks + ((ks * 64 + key) * 4 + (lg ^ swzk(key))) * 8);
+                    sacc[f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[ks], sacc[f], 0, 0, 0);
+                }
+            }
+            // lane (lr, lg), fragment f, reg r  <->  key kv0 + 32*(f>>1) + lg*8 + (f&1)*4 + r, query lr
+            float mx = -1e30f;
+#pragma unroll
+            for (int f = 0; f < 4; ++f)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                    const int key = kv0 + 32 * (f >> 1) + lg * 8 + (f & 1) * 4 + rr;
+                    if (key >= a.nk_frame) sacc[f][rr] = -1e30f;
+                    mx = fmaxf(mx, sacc[f][rr]);
+                }
+            mx = fmaxf(mx, __shfl_xor(mx, 16));
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+            const float m_new = fmaxf(m_run, mx);
+            const float alpha = __expf(m_run - m_new);
+            m_run = m_new;
+            float psum = 0.f;
+            half8 pf[2];
+#pragma unroll
+            for (int f = 0; f < 4; ++f)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) {
+                    const float pv = __expf(sacc[f][rr] - m_new);
+                    psum += pv;
+                    pf[f >> 1][(f & 1) * 4 + rr] = (half_t)pv;
+                }
+            l_run = l_run * alpha + psum;
+#pragma unroll
+            for (int t = 0; t < SR_TF; ++t)
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) o[t][rr] *= alpha;
+            // ---- O^T[dv][query] += V^T[dv][key] P^T[key][query] ----
+#pragma unroll
+            for (int t = 0; t < SR_TF; ++t) {
+                const int row = t * 16 + lr;
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const half8 vf = *reinterpret_cast<const half8*>(Vs + ((s * SR_DV + row) * 4 + (lg ^ swzr(row))) * 8);
+                    o[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf[s], o[t], 0, 0, 0);
+                }
+            }
+        }
+    }
+    l_run += __shfl_xor(l_run, 16);
+    l_run += __shfl_xor(l_run, 32);
+    if (!q_ok) return;
+    const float inv = a.gamma / l_run;
+    const half_t* xr = a.x + qf_ * a.x_fs + (int64_t)qp * a.x_pitch + a.x_coff;
+    half_t* orow = a.out + qf_ * a.o_fs + (int64_t)qp * a.o_pitch + a.o_coff;
+#pragma unroll
+    for (int t = 0; t < SR_TF; ++t) {
+        const int c = t * 16 + lg * 4;
+        const half4 xv = *reinterpret_cast<const half4*>(xr + c);
+        half4 ov;
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) ov[rr] = (half_t)(o[t][rr] * inv + (float)xv[rr]);
+        *reinterpret_cast<half4*>(orow + c) = ov;
+    }
+}
+
+// ---- temporal stacking: dst[t][p][kt * C + c] = src[t + kt - 1][p][c], zeros outside [0, T) ----
+__global__ void tstack_kernel(const half_t* __restrict__ x, half_t* __restrict__ y, int T, int64_t P, int C8, int x_cp, int x_co, int64_t x_fs, int y_cp,
+                              int y_co, int64_t y_fs) {
+    const int64_t total = (int64_t)T * P * 3 * C8;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C8);
+        const int kt = (int)((i / C8) % 3);
+        const int64_t p = (i / (3 * C8)) % P;
+        const int t = (int)(i / (3 * C8 * P));
+        const int ts = t + kt - 1;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (ts >= 0 && ts < T) v = *reinterpret_cast<const uint4*>(x + ts * x_fs + p * x_cp + x_co + c * 8);
+        *reinterpret_cast<uint4*>(y + t * y_fs + p * y_cp + y_co + (kt * C8 + c) * 8) = v;
+    }
+}
+
+__global__ void elu_kernel(const half_t* __restrict__ x, half_t* __restrict__ y, int B, int64_t P, int C8, int x_cp, int x_co, int64_t x_fs, int y_cp, int y_co,
+                           int64_t y_fs) {
+    const int64_t total = (int64_t)B * P * C8;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C8);
+        const int64_t p = (i / C8) % P;
+        const int b = (int)(i / (C8 * P));
+        half8 v = *reinterpret_cast<const half8*>(x + b * x_fs + p * x_cp + x_co + c * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float f = (float)v[e];
+            v[e] = (half_t)(f > 0.f ? f : expm1f(f));
+        }
+        *reinterpret_cast<half8*>(y + b * y_fs + p * y_cp + y_co + c * 8) = v;
+    }
+}
+
+__device__ __forceinline__ int cv_gray(int r, int g, int b) { return (4899 * r + 9617 * g + 1868 * b + 8192) >> 14; }   // OpenCV COLOR_RGB2GRAY, 8 bit
+
+__global__ void prep_remaster_kernel(const uint8_t* __restrict__ rgb, half_t* __restrict__ y, int B, int Hi, int Wi, int Ho, int Wo, int refs, int y_cp, int y_co,
+                                     int64_t y_fs) {
+    const int64_t total = (int64_t)B * Ho * Wo;
+    const int padv = refs ? 0 : 1;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int xo = (int)(i % Wo), yo = (int)((i / Wo) % Ho), b = (int)(i / ((int64_t)Wo * Ho));
+        const int xs = min(max(xo - padv, 0), Wi - 1), ys = min(max(yo - padv, 0), Hi - 1);
+        const uint8_t* p = rgb + (((int64_t)b * Hi + ys) * Wi + xs) * 3;
+        half8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (half_t)0.f;
+        if (refs) {
+#pragma unroll
+            for (int e = 0; e < 3; ++e) o[e] = (half_t)((float)p[e] / 255.f - 0.48f);
+        } else {
+            o[0] = (half_t)((float)cv_gray(p[0], p[1], p[2]) / 255.f - 0.4462414f);
+        }
+        *reinterpret_cast<half8*>(y + b * y_fs + ((int64_t)yo * Wo + xo) * y_cp + y_co) = o;
+    }
+}
+
+// skimage lab2rgb in fp64, as zhang.hip states it (same constants: D65 white, scipy's inverse of the sRGB matrix)
+__device__ __forceinline__ double lab_finv(double t) { return t > 0.2068966 ? t * t * t : (t - 16.0 / 116.0) / 7.787; }
+__device__ __forceinline__ double linear_to_srgb(double c) { return c > 0.0031308 ? 1.055 * pow(c, 1.0 / 2.4) - 0.055 : c * 12.92; }
+__constant__ double kRmRgbFromXyz[9] = {3.240481343200526, -1.5371515162713185, -0.4985363261688878,
+                                        -0.9692549499965682, 1.8759900014898907, 0.04155592655829284,
+                                        0.05564663913517716, -0.20404133836651123, 1.0573110696453443};
+
+__global__ void remaster_out_kernel(const half_t* __restrict__ ab, int ab_cp, int ab_co, int64_t ab_fs, const uint8_t* __restrict__ rgb_in, uint8_t* __restrict__ out,
+                                    float* __restrict__ ab_out, int B, int64_t P) {
+    const int64_t total = (int64_t)B * P;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int b = (int)(i / P);
+        const int64_t p = i - b * P;
+        const half_t* v = ab + b * ab_fs + p * ab_cp + ab_co;
+        const float sa = 1.f / (1.f + expf(-(float)v[0])), sb = 1.f / (1.f + expf(-(float)v[1]));
+        if (ab_out) { ab_out[i * 2] = sa; ab_out[i * 2 + 1] = sb; }
+        const uint8_t* px = rgb_in + i * 3;
+        const float Lf = (float)cv_gray(px[0], px[1], px[2]) / 255.f * 100.f;
+        const float af = fminf(fmaxf(sa * 255.f - 128.f, -100.f), 100.f), bf = fminf(fmaxf(sb * 255.f - 128.f, -100.f), 100.f);
+        const double fy = ((double)Lf + 16.0) / 116.0;
+        const double fx = (double)af / 500.0 + fy;
+        double fz = fy - (double)bf / 200.0;
+        fz = fz < 0.0 ? 0.0 : fz;
+        const double X = lab_finv(fx) * 0.95047, Y = lab_finv(fy), Z = lab_finv(fz) * 1.08883;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            const double c = linear_to_srgb(kRmRgbFromXyz[3 * e] * X + kRmRgbFromXyz[3 * e + 1] * Y + kRmRgbFromXyz[3 * e + 2] * Z);
+            out[i * 3 + e] = (uint8_t)(int)(fmin(fmax(c, 0.0), 1.0) * 255.0);
+        }
+    }
+}
+
+int srcref_lds_optin() {
+    static std::mutex mu;
+    static uint64_t done = 0;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const uint64_t bit = 1ull << (dev & 63);
+    std::lock_guard<std::mutex> lk(mu);
+    if (done & bit) return 0;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(srcref_attention_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SR_LDS_BYTES);
+    if (e != hipSuccess) return (int)e;
+    done |= bit;
+    return 0;
+}
+
+}  // namespace
+
+bool srcref_attention_supported(int d, int dv) { return d == SR_D && dv == SR_DV; }
+
+int launch_srcref_attention(const half_t* q, int q_pitch, int q_coff, int64_t q_fs, const half_t* k, int64_t k_fs, const half_t* vT, int npitch, int64_t v_fs,
+                            const half_t* x, int x_pitch, int x_coff, int64_t x_fs, half_t* out, int o_pitch, int o_coff, int64_t o_fs, int T, int nq_frame,
+                            int Tr, int nk_frame, float gamma, hipStream_t s) {
+    if (T < 1 || nq_frame < 1 || Tr < 1 || nk_frame < 1 || (npitch & 63) || npitch < nk_frame || (q_pitch & 7) || (q_coff & 7) || (x_pitch & 3) || (x_coff & 3) ||
+        (o_pitch & 3) || (o_coff & 3) || (int64_t)T * nq_frame > 0x7fffffff)
+        return (int)hipErrorInvalidValue;
+    if (int e = srcref_lds_optin()) return e;
+    SrAttnArgs a{q, k, vT, x, out, q_pitch, q_coff, x_pitch, x_coff, o_pitch, o_coff, npitch, q_fs, k_fs, v_fs, x_fs, o_fs, nq_frame, T * nq_frame, nk_frame, Tr, gamma};
+    hipLaunchKernelGGL(srcref_attention_kernel, dim3((a.NQ + 63) / 64), dim3(256), SR_LDS_BYTES, s, a);
+    return (int)hipGetLastError();
+}
+
+int launch_tstack(const half_t* x, half_t* y, int T, int64_t P, int C, int x_cp, int x_co, int64_t x_fs, int y_cp, int y_co, int64_t y_fs, hipStream_t s) {
+    if ((C & 7) || (x_cp & 7) || (x_co & 7) || (y_cp & 7) || (y_co & 7)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(tstack_kernel, dim3(grid_for((int64_t)T * P * 3 * (C / 8))), dim3(256), 0, s, x, y, T, P, C / 8, x_cp, x_co, x_fs, y_cp, y_co, y_fs);
+    return (int)hipGetLastError();
+}
+
+int launch_elu(const half_t* x, half_t* y, int B, int64_t P, int C, int x_cp, int x_co, int64_t x_fs, int y_cp, int y_co, int64_t y_fs, hipStream_t s) {
+    if ((C & 7) || (x_cp & 7) || (x_co & 7) || (y_cp & 7) || (y_co & 7)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(elu_kernel, dim3(grid_for((int64_t)B * P * (C / 8))), dim3(256), 0, s, x, y, B, P, C / 8, x_cp, x_co, x_fs, y_cp, y_co, y_fs);
+    return (int)hipGetLastError();
+}
+
+int launch_prep_remaster(const uint8_t* rgb, half_t* y, int B, int Hi, int Wi, int Ho, int Wo, int refs, int y_cp, int y_co, int64_t y_fs, hipStream_t s) {
+    if ((y_cp & 7) || (y_co & 7)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(prep_remaster_kernel, dim3(grid_for((int64_t)B * Ho * Wo)), dim3(256), 0, s, rgb, y, B, Hi, Wi, Ho, Wo, refs, y_cp, y_co, y_fs);
+    return (int)hipGetLastError();
+}
+
+int launch_remaster_out(const half_t* ab, int ab_cp, int ab_co, int64_t ab_fs, const uint8_t* rgb_in, uint8_t* out, float* ab_out, int B, int64_t P, hipStream_t s) {
+    hipLaunchKernelGGL(remaster_out_kernel, dim3(grid_for((int64_t)B * P)), dim3(256), 0, s, ab, ab_cp, ab_co, ab_fs, rgb_in, out, ab_out, B, P);
+    return (int)hipGetLastError();
+}
+
+void preload_remaster() { (void)srcref_lds_optin(); (void)hipGetLastError(); }

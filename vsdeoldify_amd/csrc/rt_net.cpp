@@ -437,6 +437,63 @@ int run_op(havc_net* n, const havc_op& op, int batch) {
             e = launch_planar_out((const half_t*)bufptr(n, op.src), op.src_cpitch, op.src_coff, n->bufdesc[op.src].elems_per_frame, (float*)bufptr(n, op.dst),
                                   n->bufdesc[op.dst].elems_per_frame, batch, op.Hi * op.Wi, op.Ci, op.kh, s);
             break;
+        case HAVC_OP_SRCREF_ATTN: {
+            const int nb = (int)n->bufs.size();
+            const int Tr = op.kw > 0 ? op.kw : batch, nk = op.Ho * op.Wo;
+            if (op.src2 < 0 || op.aux0 < 0 || op.aux0 >= nb || op.aux1 < 0 || op.aux1 >= nb || !srcref_attention_supported(op.kh, op.Ci) || nk < 1 ||
+                op.src_coff + op.Ci > op.src_cpitch || op.dst_coff + op.Ci > op.dst_cpitch || op.res_coff + op.kh > op.res_cpitch)
+                return fail(c, HAVC_E_INVALID, "source-reference attention op: query / key / value buffers, 64 key and 512 value channels");
+            const uint64_t q_fs = n->bufdesc[op.src2].elems_per_frame, k_fs = n->bufdesc[op.aux0].elems_per_frame, v_fs = n->bufdesc[op.aux1].elems_per_frame;
+            const uint64_t x_fs = n->bufdesc[op.src].elems_per_frame, o_fs = n->bufdesc[op.dst].elems_per_frame, nq = (uint64_t)op.Hi * op.Wi;
+            // the net's own allocations hold max_batch frames; a bound buffer (the reference ring) is the caller's to size
+            const bool own_kv = n->bound.empty() || (!n->bound[op.aux0] && !n->bound[op.aux1]);
+            if (n->bufdesc[op.src2].elem_bytes != 2 || n->bufdesc[op.aux0].elem_bytes != 2 || n->bufdesc[op.aux1].elem_bytes != 2 || q_fs < nq * op.res_cpitch ||
+                x_fs < nq * op.src_cpitch || o_fs < nq * op.dst_cpitch || k_fs < (uint64_t)nk * op.kh || (op.Kc & 63) || op.Kc < nk ||
+                v_fs < (uint64_t)op.Ci * op.Kc || (own_kv && Tr > n->max_batch))
+                return fail(c, HAVC_E_INVALID, "source-reference attention op: buffer sizes / value pitch (Kc % 64 == 0, Kc >= keys per frame) / reference frames");
+            e = launch_srcref_attention((const half_t*)bufptr(n, op.src2), op.res_cpitch, op.res_coff, (int64_t)q_fs, (const half_t*)bufptr(n, op.aux0), (int64_t)k_fs,
+                                        (const half_t*)bufptr(n, op.aux1), op.Kc, (int64_t)v_fs, (const half_t*)bufptr(n, op.src), op.src_cpitch, op.src_coff,
+                                        (int64_t)x_fs, (half_t*)bufptr(n, op.dst), op.dst_cpitch, op.dst_coff, (int64_t)o_fs, batch, (int)nq, Tr, nk, op.f0, s);
+            break;
+        }
+        case HAVC_OP_TSTACK:
+            if ((op.Ci & 7) || op.Co != 3 * op.Ci || op.src_coff + op.Ci > op.src_cpitch || op.dst_coff + op.Co > op.dst_cpitch ||
+                (uint64_t)n->bufdesc[op.src].elems_per_frame < (uint64_t)op.Hi * op.Wi * op.src_cpitch ||
+                (uint64_t)n->bufdesc[op.dst].elems_per_frame < (uint64_t)op.Hi * op.Wi * op.dst_cpitch || op.src == op.dst)
+                return fail(c, HAVC_E_INVALID, "temporal-stack op: Co = 3 Ci, views inside their buffers, distinct buffers");
+            e = launch_tstack((const half_t*)bufptr(n, op.src), (half_t*)bufptr(n, op.dst), batch, (int64_t)op.Hi * op.Wi, op.Ci, op.src_cpitch, op.src_coff,
+                              n->bufdesc[op.src].elems_per_frame, op.dst_cpitch, op.dst_coff, n->bufdesc[op.dst].elems_per_frame, s);
+            break;
+        case HAVC_OP_ELU:
+            if ((op.Ci & 7) || op.src_coff + op.Ci > op.src_cpitch || op.dst_coff + op.Ci > op.dst_cpitch ||
+                (uint64_t)n->bufdesc[op.src].elems_per_frame < (uint64_t)op.Hi * op.Wi * op.src_cpitch ||
+                (uint64_t)n->bufdesc[op.dst].elems_per_frame < (uint64_t)op.Hi * op.Wi * op.dst_cpitch)
+                return fail(c, HAVC_E_INVALID, "elu op: views inside their buffers");
+            e = launch_elu((const half_t*)bufptr(n, op.src), (half_t*)bufptr(n, op.dst), batch, (int64_t)op.Hi * op.Wi, op.Ci, op.src_cpitch, op.src_coff,
+                           n->bufdesc[op.src].elems_per_frame, op.dst_cpitch, op.dst_coff, n->bufdesc[op.dst].elems_per_frame, s);
+            break;
+        case HAVC_OP_PREP_REMASTER: {
+            const int refs = op.flags & 1, padv = refs ? 0 : 2;
+            if (op.Hi < 1 || op.Wi < 1 || op.Ho != op.Hi + padv || op.Wo != op.Wi + padv || n->bufdesc[op.src].elem_bytes != 1 ||
+                (uint64_t)n->bufdesc[op.src].elems_per_frame != (uint64_t)op.Hi * op.Wi * 3 || op.dst_coff + 8 > op.dst_cpitch ||
+                (uint64_t)n->bufdesc[op.dst].elems_per_frame < (uint64_t)op.Ho * op.Wo * op.dst_cpitch)
+                return fail(c, HAVC_E_INVALID, "remaster prep op: u8 RGB source of Hi x Wi, destination of Hi + 2 x Wi + 2 (frames) or Hi x Wi (references)");
+            e = launch_prep_remaster((const uint8_t*)bufptr(n, op.src), (half_t*)bufptr(n, op.dst), batch, op.Hi, op.Wi, op.Ho, op.Wo, refs, op.dst_cpitch, op.dst_coff,
+                                     n->bufdesc[op.dst].elems_per_frame, s);
+            break;
+        }
+        case HAVC_OP_REMASTER_OUT: {
+            const uint64_t P = (uint64_t)op.Hi * op.Wi;
+            const bool tap = op.aux0 >= 0;
+            if (op.src2 < 0 || n->bufdesc[op.src2].elem_bytes != 1 || (uint64_t)n->bufdesc[op.src2].elems_per_frame != P * 3 || n->bufdesc[op.dst].elem_bytes != 1 ||
+                (uint64_t)n->bufdesc[op.dst].elems_per_frame != P * 3 || op.src_coff + 2 > op.src_cpitch ||
+                (uint64_t)n->bufdesc[op.src].elems_per_frame < P * op.src_cpitch ||
+                (tap && (op.aux0 >= (int)n->bufs.size() || n->bufdesc[op.aux0].elem_bytes != 4 || (uint64_t)n->bufdesc[op.aux0].elems_per_frame != P * 2)))
+                return fail(c, HAVC_E_INVALID, "remaster output op: u8 RGB input (src2) and output of Hi x Wi, optional fp32 [Hi * Wi][2] tap buffer (aux0)");
+            e = launch_remaster_out((const half_t*)bufptr(n, op.src), op.src_cpitch, op.src_coff, n->bufdesc[op.src].elems_per_frame, (const uint8_t*)bufptr(n, op.src2),
+                                    (uint8_t*)bufptr(n, op.dst), tap ? (float*)bufptr(n, op.aux0) : nullptr, batch, (int64_t)P, s);
+            break;
+        }
         default:
             return fail(c, HAVC_E_INVALID, "unknown op type");
     }

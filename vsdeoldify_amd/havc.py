@@ -6,6 +6,7 @@
     HAVC_SceneDetect vsdeoldify/__init__.py:3191-3225     (-> scdetect.SceneInfo: arrays carry no frame props)
     HAVC_deepex      vsdeoldify/__init__.py:1421-1735     (ex_model 0 = ColorMNet, method 0; `scenes=` is the SceneInfo the reference reads off clip_ref's props)
     HAVC_bw_tune     vsdeoldify/__init__.py:1266-1339     HAVC_auto_levels vsdeoldify/__init__.py:3150-3179   (methods 0-3: CLAHE / equalizeHist; equalize.py)
+    HAVC_DeepRemaster vsdeoldify/__init__.py:2689-2735    (mode 0: reference stills from a directory; remaster_render.RemasterRender; fast mode only)
 
 Same names, argument lists, defaults, parameter normalisation, frame-size rule, model routing, combine dispatch
 (vsslib/mcomb.py:125-192) and error texts; a "clip" is a uint8 array [n, h, w, 3] (or one frame [h, w, 3], or a
@@ -891,3 +892,55 @@ def HAVC_bw_tune(clip=None, bw_tune='Light', bw_method=0, luma_blend=True, range
     return _equalize_clip(clip, device_index, method=bw_method, strength=b_strength[bw_id], weight3=w_strength[bw_id], luma_blend=luma_blend,
                           range_tv=range_tv, range_tv_tables=bool(range_tv),
                           balance=(w_strength[bw_id], [r_factor[bw_id], g_factor[bw_id], b_factor[bw_id]]))       # :1328-1333
+
+
+# ---- HAVC_DeepRemaster (vsdeoldify/__init__.py:2689-2735 -> remaster/__init__.py:203-307 vs_remaster_colorize) ----------------------------------------
+def HAVC_DeepRemaster(clip, length=2, render_vivid=False, ref_dir=None, ref_minedge=256, frame_mindim=320, ref_buffer_size=20, device_index=0,
+                      inference_mode=False, mode=0, *, state_dict=None, model=None, weights_dir=None):
+    """DeepRemaster with reference stills from a directory (mode 0): the clip is brought to the inference size (resize_for_inference: the shorter side
+    to frame_mindim, both sides to multiples of 16; the library's Spline64 for zimg's), runs through RemasterRender in batches of `length` frames
+    (the last batch may be shorter; the window of stills moves with the batch's last frame number), goes back to its size with Spline64 and keeps
+    its own luma (vs_recover_resolution = chroma_post_process with the source as luma, fused into the resize).  ndarray in -> ndarray out; a DeviceImage
+    clip stays in HBM.  inference_mode is accepted and ignored (a torch switch).  Refused, not approximated: render_vivid=True (vs_tweak: a zimg YUV420
+    round trip) and mode=1 (reference frames through VapourSynth clips and scene-change props).  Keyword-only extras of this library: state_dict / model
+    (seeded NetworkC weights or a built RemasterColorNet instead of weights_dir/remasternet.pth.tar)."""
+    if clip is None or not (is_device(clip) or isinstance(clip, np.ndarray)):
+        raise HAVCError("HAVC_DeepRemaster: this is not a clip")
+    if ref_dir is None:
+        raise HAVCError("HAVC_DeepRemaster: ref_dir is unset")
+    if mode != 0:
+        raise NotImplementedError("HAVC_DeepRemaster: mode = 1 reads its reference frames through VapourSynth clips and scene-change frame props: only mode = 0 "
+                                  "(direct access to the reference frame folder) is built")
+    if not os.path.isdir(ref_dir):
+        raise HAVCError(f"HAVC_DeepRemaster: '{ref_dir}' is not a valid directory")
+    if length < 2:
+        raise HAVCError("HAVC_DeepRemaster: length must be at least 2")
+    if render_vivid:
+        raise NotImplementedError("HAVC_DeepRemaster: render_vivid is vs_tweak (a zimg YUV420 round trip): not in this harness")
+    from .remaster_render import RemasterRender, get_ref_list, resize_for_inference_size
+    if not get_ref_list(ref_dir)[0]:
+        raise HAVCError(f"HAVC_DeepRemaster: no reference frames found in {ref_dir}")
+    clip, single = _as_clip(clip)
+    n, h, w = clip.shape[0], clip.shape[1], clip.shape[2]
+    fw, fh = resize_for_inference_size(w, h, frame_mindim)
+    # ---- everything below touches the GPU ----
+    engine = RemasterRender(device_index=device_index, ref_minedge=ref_minedge, ref_buffer_size=ref_buffer_size, length=length, model_dir=weights_dir,
+                            state_dict=state_dict, model=model)
+    try:
+        engine.load_ref_dir(ref_dir)
+        ctx = engine._ctx()
+        host_in = not is_device(clip)
+        dclip = DeviceImage.from_numpy(ctx, clip) if host_in else clip
+        small = spline64(ctx, dclip, fw, fh)
+        colored = DeviceImage(ctx, small.shape)
+        for n0 in range(0, n, length):
+            n1 = min(n0 + length, n)
+            colored.frames(n0, n1).copy_from(engine.process_frames(small.frames(n0, n1), last_frame_idx=min(n0 + length - 1, n - 1)))
+        out = spline64(ctx, colored, w, h, luma_from=dclip)
+        if host_in:
+            out = out.numpy()
+            return out[0] if single else out
+        ctx.synchronize()
+        return out.reshaped(out.shape[1:]) if single else out
+    finally:
+        engine.close()

@@ -509,6 +509,39 @@ class PlanBuilder:
         return self._op(name, type=nat.OP_PLANAR_OUT, src=x.buf, src_coff=x.coff + coff, src_cpitch=x.cpitch, dst=dst_buf, Hi=x.H, Wi=x.W, Ci=C,
                         Ho=x.H, Wo=x.W, Co=C, kh=act)
 
+    # ---- DeepRemaster ops (csrc/remaster.hip) ----
+    def srcref_attn(self, name, x, q, k_buf, vT_buf, npitch, ref_hw, y, gamma, ref_frames=0):
+        """SourceReferenceAttention: x / y = source and result views (512 channels), q = query view (64 channels) of the same grid; k_buf = packed
+        64-channel key rows and vT_buf = transposed values [512][npitch], both one entry per reference frame of ref_hw tokens; ref_frames = 0: the keys
+        are the batch's own frames (self-attention)."""
+        assert x.C == y.C == x.span == 512 and q.C == 64 and q.H == x.H and q.W == x.W and npitch % 64 == 0 and npitch >= ref_hw[0] * ref_hw[1], name
+        nq, nk = x.H * x.W, ref_hw[0] * ref_hw[1]
+        return self._op(name, type=nat.OP_SRCREF_ATTN, src=x.buf, src_coff=x.coff, src_cpitch=x.cpitch, dst=y.buf, dst_coff=y.coff, dst_cpitch=y.cpitch,
+                        src2=q.buf, res_coff=q.coff, res_cpitch=q.cpitch, aux0=k_buf, aux1=vT_buf, Kc=npitch, Hi=x.H, Wi=x.W, Ci=x.C, Ho=ref_hw[0], Wo=ref_hw[1],
+                        Co=x.C, kh=q.C, kw=ref_frames, f0=gamma, flops=2 * nq * nk * max(ref_frames, 1) * (q.C + x.C))
+
+    def tstack(self, name, x, y):
+        """frames t-1, t, t+1 of x side by side in y's channels (zeros outside the batch): the input of a (3,3,3) conv run as a 3 x 3 conv"""
+        assert y.span == 3 * x.span and x.H == y.H and x.W == y.W and x.buf != y.buf, name
+        return self._op(name, type=nat.OP_TSTACK, src=x.buf, src_coff=x.coff, src_cpitch=x.cpitch, dst=y.buf, dst_coff=y.coff, dst_cpitch=y.cpitch,
+                        Hi=x.H, Wi=x.W, Ci=x.span, Ho=y.H, Wo=y.W, Co=y.span)
+
+    def elu(self, name, x, y=None):
+        y = y or x
+        assert x.span == y.span and x.H == y.H and x.W == y.W, name
+        return self._op(name, type=nat.OP_ELU, src=x.buf, src_coff=x.coff, src_cpitch=x.cpitch, dst=y.buf, dst_coff=y.coff, dst_cpitch=y.cpitch,
+                        Hi=x.H, Wi=x.W, Ci=x.span, Ho=y.H, Wo=y.W, Co=y.span)
+
+    def prep_remaster(self, name, in_buf, H, W, y, refs=False):
+        pad = 0 if refs else 2
+        assert y.H == H + pad and y.W == W + pad and y.span == 8, name
+        return self._op(name, type=nat.OP_PREP_REMASTER, flags=1 if refs else 0, src=in_buf, dst=y.buf, dst_coff=y.coff, dst_cpitch=y.cpitch, Hi=H, Wi=W,
+                        Ci=8, Ho=y.H, Wo=y.W, Co=8)
+
+    def remaster_out(self, name, x, in_buf, out_buf, ab_buf=-1):
+        return self._op(name, type=nat.OP_REMASTER_OUT, src=x.buf, src_coff=x.coff, src_cpitch=x.cpitch, src2=in_buf, dst=out_buf, aux0=ab_buf, Hi=x.H, Wi=x.W,
+                        Ci=2, Ho=x.H, Wo=x.W, Co=3)
+
     def finish(self):
         ops = np.array(self.ops, dtype=nat.OP_DTYPE)
         bufs = np.array(self.bufs, dtype=nat.BUF_DTYPE)

@@ -521,3 +521,81 @@ def synth_colormnet_state_dict(seed=0):
             sd[name] = n(np.sqrt(2.0 / fan_in))
     _CACHE[key] = sd
     return sd
+
+
+# ---- DeepRemaster colour network (remaster/model/remasternet.py:103-187 NetworkC) -----------------------------------------------
+def remaster_state_dict_spec():
+    """name -> shape in the order of the reference's NetworkC().state_dict() (checked against tests/golden/spec_remaster.json, dumped from
+    the reference module)."""
+    spec = OrderedDict()
+
+    def tconv(p, ci, co, kt=1, bn=True):
+        spec[p + ".conv3d.weight"], spec[p + ".conv3d.bias"] = (co, ci, kt, 3, 3), (co,)
+        if bn:
+            _bn(spec, p + ".bn", co)
+
+    def attn(p, c=512):
+        spec[p + ".gamma"] = (1,)
+        for nm, co in (("query_conv", c // 8), ("key_conv", c // 8), ("value_conv", c)):
+            spec[f"{p}.{nm}.weight"], spec[f"{p}.{nm}.bias"] = (co, c, 1, 1, 1), (co,)
+
+    def stack(p, chans, first=0):
+        for i, (ci, co) in enumerate(chans):
+            tconv(f"{p}.{first + i}", ci, co)
+
+    enc = [(64, 128), (128, 128), (128, 256), (256, 256), (256, 256), (256, 512), (512, 512), (512, 512)]
+    stack("down1", [(1, 64)] + enc, first=1)                      # down1.0 is the ReplicationPad3d
+    stack("flat", [(512, 512)] * 2)
+    stack("down2", [(512, 512)] * 2)
+    attn("stattn1"); attn("stattn2"); attn("selfattn1")
+    tconv("conv1", 512, 512)
+    tconv("up1.conv3d", 1024, 512, kt=3)
+    attn("selfattn2")
+    tconv("conv2", 512, 256, kt=3)
+    for p, (a, b_, c) in (("up2", (256, 128, 64)), ("up3", (64, 32, 16))):
+        tconv(p + ".0", a, b_, kt=3)
+        tconv(p + ".1", b_, c, kt=3)
+    tconv("up4.0", 16, 8, kt=3)
+    spec["up4.1.weight"], spec["up4.1.bias"] = (2, 8, 3, 3, 3), (2,)
+    stack("reffeatnet1", [(3, 64)] + enc)
+    stack("reffeatnet2", [(512, 512)] * 3)
+    return spec
+
+
+def synth_remaster_state_dict(seed=0):
+    """Seeded synthetic NetworkC weights (remasternet.pth.tar cannot be fetched offline).  Conv + BatchNorm3d + ELU stacks keep O(1) activations
+    (ELU passes about half the variance of a unit Gaussian plus a negative mean, which the BatchNorm statistics below absorb); the four attention
+    gammas are 0.5-0.8, not the reference's initial 0, and the query / key scales give logits with a standard deviation of 1-3 (neither one-hot nor
+    uniform); the last conv is damped so that the sigmoid stays in its steep part."""
+    key = ("remaster", int(seed))
+    if key in _CACHE:
+        return _CACHE[key]
+    spec = remaster_state_dict_spec()
+    sd = OrderedDict()
+    for name, shape in spec.items():
+        r = _rng(seed, "remaster." + name)
+        parent, leaf = name.rsplit(".", 1)
+        is_bn = (parent + ".running_mean") in spec
+        n = lambda s: (r.standard_normal(shape) * s).astype(np.float32)
+        fan_in = int(np.prod(shape[1:])) if len(shape) > 1 else 1
+        if leaf == "num_batches_tracked":
+            sd[name] = np.array(1000, np.int64)
+        elif is_bn:
+            sd[name] = {"weight": r.uniform(0.8, 1.2, shape), "bias": r.standard_normal(shape) * 0.1,
+                        "running_mean": r.standard_normal(shape) * 0.1, "running_var": r.uniform(0.7, 1.3, shape)}[leaf].astype(np.float32)
+        elif leaf == "gamma":
+            sd[name] = r.uniform(0.5, 0.8, shape).astype(np.float32)
+        elif leaf == "bias":
+            sd[name] = n(0.05)
+        elif "query_conv" in name or "key_conv" in name:
+            sd[name] = n(0.65 / np.sqrt(fan_in))
+        elif "value_conv" in name:
+            sd[name] = n(1.0 / np.sqrt(fan_in))
+        elif name == "up4.1.weight":
+            sd[name] = n(2.5 / np.sqrt(fan_in))
+        elif name in ("down1.1.conv3d.weight", "reffeatnet1.0.conv3d.weight"):      # inputs of standard deviation ~0.25
+            sd[name] = n(5.0 / np.sqrt(fan_in))
+        else:
+            sd[name] = n(np.sqrt(1.6 / fan_in))
+    _CACHE[key] = sd
+    return sd
