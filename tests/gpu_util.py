@@ -14,20 +14,32 @@ def nhwc_pad(x_nchw, span=None):
     return out
 
 
-def run_plan(ctx, pack, b, uploads, downloads, batch, cfg=0):
-    """uploads: {buf: ndarray}; downloads: {buf: (shape, dtype)} -> {buf: ndarray}."""
+def run_plan(ctx, pack, b, uploads, downloads, batch, cfg=0, max_batch=None, bound=None):
+    """uploads: {buf: ndarray}; downloads: {buf: (shape, dtype)} -> {buf: ndarray}.
+    max_batch: frames the net is created for (default: batch; larger = a short batch on a bigger net).
+    bound: {buf: ndarray} -> the array goes into device memory of the caller's own and the buffer is bound to it (havc_net_bind), as RemasterSession
+    does with its reference ring: such a buffer may hold more frames than the net's own allocations."""
     ops, bufs = b.finish()
     ops["reserved"] = cfg
     w = nat.Weights(ctx, pack.blob() or b"\0" * 256)
-    net = nat.Net(ctx, w, ops, bufs, 0, 0, 0, batch)
+    net = nat.Net(ctx, w, ops, bufs, 0, 0, 0, max_batch or batch)
+    mine = []
     try:
         for k, v in uploads.items():
             net.upload(k, v)
+        for k, v in (bound or {}).items():
+            v = np.ascontiguousarray(v)
+            d = ctx.dev_alloc(v.nbytes + 256)
+            mine.append(d)
+            ctx.dev_upload(d, v)
+            net.bind(k, d)
         net.run_ops(0, len(ops), batch)
         return {k: net.download(k, shp, dt) for k, (shp, dt) in downloads.items()}
     finally:
         net.close()
         w.close()
+        for d in mine:
+            ctx.dev_free(d)
 
 
 def conv_op(ctx, x, W, bias=None, scale=None, shift=None, stride=1, pad=0, dil=1, flags=0, res=None, pixshuf=False, cfg=0):

@@ -189,7 +189,7 @@ __global__ void elu_kernel(const half_t* __restrict__ x, half_t* __restrict__ y,
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float f = (float)v[e];
-            v[e] = (half_t)(f > 0.f ? f : expm1f(f));
+            v[e] = (half_t)(f >= 0.f ? f : expm1f(f));          // >= : -0 stays -0 (the device expm1f returns +0 for it); NaN still goes through expm1f
         }
         *reinterpret_cast<half8*>(y + b * y_fs + p * y_cp + y_co + c * 8) = v;
     }
