@@ -12,6 +12,7 @@ from vsdeoldify_amd.render import get_context
 
 SHAPES = {  # name: (Cin, Cout, k, stride, pad, H, W, flags)
     "tail259": (259, 259, 3, 1, 1, 560, 560, nat.F_RELU_PRE),
+    "tail259rgb8": (259, 259, 3, 1, 1, 560, 560, nat.F_RELU_PRE | nat.F_RESIDUAL | nat.F_FUSE_RGB8),   # the second tail conv: + residual + layers.11 + SigmoidRange -> u8
     "tail256": (256, 256, 3, 1, 1, 560, 560, nat.F_RELU_PRE),
     "tailA320": (320, 256, 3, 1, 1, 560, 560, nat.F_RELU_PRE),      # stagger experiment: no extra column fragment, 640-byte pitch
     "tailB272": (256, 259, 3, 1, 1, 560, 560, nat.F_RELU_PRE),      #   extra column fragment, 512-byte input pitch
@@ -61,9 +62,27 @@ SHAPES = {  # name: (Cin, Cout, k, stride, pad, H, W, flags)
 }
 
 
+def frames(r, batch, H, W, C):
+    """fp16 [batch, H, W, C] of N(0, 0.25) values: one random frame, repeated (the generator is most of this tool's run time at 560 x 560 x 16 frames)"""
+    one = (r.standard_normal((1, H, W, C), dtype=np.float32) * 0.5).astype(np.float16)
+    return np.ascontiguousarray(np.broadcast_to(one, (batch, H, W, C)))
+
+
+def add_conv(b, pack, name, pc, x, y, res, r, **kw):
+    """b.conv, and for a HAVC_F_FUSE_RGB8 shape the fused 1x1 weights / bias and the u8 output buffer as deoldify_net.py attaches them"""
+    flags = kw["flags"]
+    if not flags & nat.F_FUSE_RGB8:
+        return b.conv(name, pc, x, y, res=res, **kw)
+    fw = np.zeros((3, pc.Npad), np.float32)
+    fw[:, :pc.Cout] = r.standard_normal((3, pc.Cout)) / np.sqrt(pc.Cout)
+    oi = b.conv(name, pc, x, y, res=res, f=(-3.0, 3.0, 0, 0), aux0=b.buf(y.H * y.W * 3, 1), **kw)
+    b.ops[oi]["scale_off"], b.ops[oi]["shift_off"] = pack.add(fw), pack.add(np.zeros(3, np.float32))
+    return oi
+
+
 def bench(ctx, name, batch, reps, cfg=0):
-    with_res = name.endswith("+res")
-    Cin, Cout, k, s, p, H, W, flags = SHAPES[name[:-4] if with_res else name]
+    with_res = name.endswith("+res") or bool(SHAPES.get(name, (0,) * 8)[7] & nat.F_RESIDUAL)
+    Cin, Cout, k, s, p, H, W, flags = SHAPES[name[:-4] if name.endswith("+res") else name]
     if with_res:
         flags |= nat.F_RESIDUAL
     r = np.random.default_rng(0)
@@ -77,16 +96,16 @@ def bench(ctx, name, batch, reps, cfg=0):
     Ho = (H + 2 * p - k) // s + 1
     y = b.tensor(2 * Ho, 2 * Ho, Cout // 4) if flags & nat.F_OUT_PIXSHUF else b.tensor(Ho, Ho, Cout)
     res = b.tensor(Ho, Ho, Cout) if with_res else None
-    b.conv(name, pc, x, y, stride=s, pad=p, flags=flags, res=res)
+    add_conv(b, pack, name, pc, x, y, res, r, stride=s, pad=p, flags=flags)
     ops, bufs = b.finish()
     ops["reserved"] = cfg
     w = nat.Weights(ctx, pack.blob())
     net = nat.Net(ctx, w, ops, bufs, 0, 0, 0, batch)
-    xin = (r.standard_normal((batch, H, W, x.span)) * 0.5).astype(np.float16)
+    xin = frames(r, batch, H, W, x.span)
     xin[..., Cin:] = 0
     net.upload(x.buf, xin)
     if with_res:
-        net.upload(res.buf, (r.standard_normal((batch, Ho, Ho, res.cpitch)) * 0.5).astype(np.float16))
+        net.upload(res.buf, frames(r, batch, Ho, Ho, res.cpitch))
     for _ in range(2):
         net.profile(batch)
     ms = float(np.median([net.profile(batch)[0] for _ in range(reps)]))

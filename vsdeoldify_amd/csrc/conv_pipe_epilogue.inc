@@ -287,23 +287,114 @@
             }
             bvs[ni] = p.bias ? *reinterpret_cast<const float4*>(p.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        float4v facc[FM];
+        // extra columns: channels nx .. nx+2 are real (x0's RGB); lane group 0 folds this wave's two extra-column fragments into three partial dot
+        // products per pixel.  Operands (bias, residual, fused weights: scalar loads, one dependent round trip) and arithmetic are split so that the
+        // RES_LDS kernels request the operands with the first residual vectors instead of behind the projection.
+        const int nx = n0 + BN;
+        float xbias[4], xw[3][4], dx[2][3];
+        half_t xres[2][4];
+        auto extra_load = [&]() {
 #pragma unroll
-        for (int mh = 0; mh < FM; mh += 4) {               // four pixel fragments at a time: 16 residual loads in flight
-            half4 rr[4][FN];
+            for (int r = 0; r < 4; ++r) {
+                xbias[r] = p.bias ? p.bias[nx + r] : 0.f;
 #pragma unroll
-            for (int mj = 0; mj < 4; ++mj) {
-                const int m = gm(wm * (FM * 16) + PF(mh + mj) * 16 + lp);
+                for (int jo = 0; jo < 3; ++jo) xw[jo][r] = (float)(half_t)p.fuse_w[jo * p.Npad + nx + r];
+            }
 #pragma unroll
-                for (int ni = 0; ni < FN; ++ni) {
-                    rr[mj][ni] = half4{0, 0, 0, 0};
-                    if ((eflags & HAVC_F_RESIDUAL) && m < p.M)
-                        rr[mj][ni] = *reinterpret_cast<const half4*>(p.res + opix(m) * p.res_cpitch + p.res_coff + nw0 + ni * 16 + lg * 4);
+            for (int i = 0; i < 2; ++i) {
+                const int m = gm(wm * (FM * 16) + (wn * 2 + i) * 16 + lp);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    xres[i][r] = (half_t)0.f;
+                    if ((eflags & HAVC_F_RESIDUAL) && m < p.M && nx + r < p.Co) xres[i][r] = p.res[opix(m) * p.res_cpitch + p.res_coff + nx + r];
                 }
             }
+        };
+        auto extra_fold = [&]() {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int m = gm(wm * (FM * 16) + (wn * 2 + i) * 16 + lp);
+                float d0 = 0.f, d1 = 0.f, d2 = 0.f;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float v = accx[i][r] + xbias[r];
+                    if (eflags & HAVC_F_RELU_PRE) v = v > 0.f ? v : (leaky ? v * p.f2 : 0.f);
+                    if ((eflags & HAVC_F_RESIDUAL) && m < p.M && nx + r < p.Co)      // as epilogue_frag: fp16, then + residual
+                        v = (float)(half_t)v + (float)xres[i][r];
+                    const float f = (float)(half_t)v;
+                    d0 += f * xw[0][r];
+                    d1 += f * xw[1][r];
+                    d2 += f * xw[2][r];
+                }
+                dx[i][0] = d0; dx[i][1] = d1; dx[i][2] = d2;
+            }
+        };
+        // The residual (the 259-channel cat tensor: as many bytes as the conv reads).  RES_LDS, the compile-time-flag kernels: it takes the road of the
+        // storing epilogue's phase 2, backwards: lane -> (pixel row lane>>3 (+8), 16-byte slot lane&7), so a wave's load touches 8 whole 128-byte lines
+        // instead of 16 lines in 32-byte runs; the vectors go into the wave-private swizzled LDS image (the layout phase 1 of the storing epilogue
+        // writes) and come back in fragment layout, one conflict-free ds_read_b64 per lane and column fragment.  Four pixel fragments (8 loads per
+        // lane) at a time; the second four are requested before the first four are consumed.  Routing only: the operands and the order of every
+        // addition are those of the direct loads.  The run-time-flag kernels and conv_halo_kernel (every layer kind's path in one register allocation:
+        // the staging registers spill there) keep the direct half4 loads in fragment layout, four fragments in flight.
+        constexpr bool RES_LDS = UNIT_STEP;
+        const bool with_res = eflags & HAVC_F_RESIDUAL;
+        const int rslot = lane & 7, rrow = lane >> 3;
+        char* img = smem + wave * (FM * 2048);
+        half8 rq[4][2];
+#define HAVC_RES_FETCH(mh)                                                                                                              \
+        _Pragma("unroll") for (int mj = 0; mj < 4; ++mj)                                                                                \
+            _Pragma("unroll") for (int hp = 0; hp < 2; ++hp) {                                                                          \
+                const int m = gm(wm * (FM * 16) + PF((mh) + mj) * 16 + rrow + hp * 8);                                                  \
+                rq[mj][hp] = half8{0, 0, 0, 0, 0, 0, 0, 0};                                                                             \
+                if (m < p.M) rq[mj][hp] = *reinterpret_cast<const half8*>(p.res + opix(m) * p.res_cpitch + p.res_coff + nw0 + rslot * 8); \
+            }
+#define HAVC_RES_STAGE(mh)                                                                                                              \
+        _Pragma("unroll") for (int mj = 0; mj < 4; ++mj)                                                                                \
+            _Pragma("unroll") for (int hp = 0; hp < 2; ++hp) {                                                                          \
+                const int px = rrow + hp * 8;                                                                                           \
+                *reinterpret_cast<half8*>(img + ((mh) + mj) * 2048 + px * 128 + ((rslot ^ (px & 7)) << 4)) = rq[mj][hp];                \
+            }
+        if (RES_LDS) {
+            if (with_res) { HAVC_RES_FETCH(0) }
+            if (lg == 0) extra_load();
+            // every wave is done reading the last stage: the images may overwrite it.  Only the LDS reads have to be over -- __syncthreads() would also
+            // drain the loads just requested (it waits for vmcnt 0 in front of the barrier)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+        }
+        HAVC_STAMP(3);
+        float4v facc[FM];
+#pragma unroll
+        for (int mh = 0; mh < FM; mh += 4) {
+            half4 rd[4][FN];                               // !RES_LDS: four pixel fragments at a time, 16 residual loads in flight
+            if (RES_LDS && with_res) {
+                HAVC_RES_STAGE(mh)
+                if (mh + 4 < FM) { HAVC_RES_FETCH(mh + 4) }
+            }
+            if (!RES_LDS) {
+#pragma unroll
+                for (int mj = 0; mj < 4; ++mj) {
+                    const int m = gm(wm * (FM * 16) + PF(mh + mj) * 16 + lp);
+#pragma unroll
+                    for (int ni = 0; ni < FN; ++ni) {
+                        rd[mj][ni] = half4{0, 0, 0, 0};
+                        if (with_res && m < p.M)
+                            rd[mj][ni] = *reinterpret_cast<const half4*>(p.res + opix(m) * p.res_cpitch + p.res_coff + nw0 + ni * 16 + lg * 4);
+                    }
+                }
+            }
+            if (mh == 0) HAVC_STAMP(10);
+            if (RES_LDS && mh == 0 && lg == 0) extra_fold();
 #pragma unroll
             for (int mj = 0; mj < 4; ++mj) {
                 const int mi = mh + mj;
+                half4 rr[FN];
+#pragma unroll
+                for (int ni = 0; ni < FN; ++ni) {
+                    if (!RES_LDS) rr[ni] = rd[mj][ni];
+                    else if (with_res) rr[ni] = *reinterpret_cast<const half4*>(img + mi * 2048 + lp * 128 + (((ni * 2 + (lg >> 1)) ^ (lp & 7)) << 4) + (lg & 1) * 8);
+                    else rr[ni] = half4{0, 0, 0, 0};
+                }
                 facc[mi] = float4v{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int ni = 0; ni < FN; ++ni) {
@@ -313,13 +404,17 @@
                     for (int r = 0; r < 4; ++r) {
                         float v = acc[ni][mi][r] + bb[r];
                         if (eflags & HAVC_F_RELU_PRE) v = v > 0.f ? v : (leaky ? v * p.f2 : 0.f);
-                        o[r] = (half_t)((float)(half_t)v + (float)rr[mj][ni][r]);    // the rounding points of the unfused chain (conv result -> fp16, + residual -> fp16)
+                        o[r] = (half_t)((float)(half_t)v + (float)rr[ni][r]);    // the rounding points of the unfused chain (conv result -> fp16, + residual -> fp16)
                     }
                     facc[mi] = __builtin_amdgcn_mfma_f32_16x16x16f16(wa[ni], o, facc[mi], 0, 0, 0);
                 }
             }
         }
-        __syncthreads();                                   // every wave is done reading the last stage
+#undef HAVC_RES_FETCH
+#undef HAVC_RES_STAGE
+        HAVC_STAMP(4);
+        __syncthreads();                                   // every wave is done reading the last stage / its image: the reduction array below aliases both
+        HAVC_STAMP(11);
         float* part = reinterpret_cast<float*>(smem);      // [5][BM][3]
         if (lg == 0) {
 #pragma unroll
@@ -327,25 +422,27 @@
                 float* q = part + (wn * BM + wm * (FM * 16) + PF(mi) * 16 + lp) * 3;
                 q[0] = facc[mi][0]; q[1] = facc[mi][1]; q[2] = facc[mi][2];
             }
-            const int nx = n0 + BN;                        // extra columns: channels nx .. nx+2 are real (x0's RGB)
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int pl = wm * (FM * 16) + (wn * 2 + i) * 16 + lp;
-                const int m = gm(pl);
-                float d0 = 0.f, d1 = 0.f, d2 = 0.f;
+                if (!RES_LDS) {                            // operands fetched here, one by one (these kernels have no registers to hold them across the projection)
+                    const int m = gm(pl);
+                    float d0 = 0.f, d1 = 0.f, d2 = 0.f;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float v = accx[i][r] + (p.bias ? p.bias[nx + r] : 0.f);
-                    if (eflags & HAVC_F_RELU_PRE) v = v > 0.f ? v : (leaky ? v * p.f2 : 0.f);
-                    if ((eflags & HAVC_F_RESIDUAL) && m < p.M && nx + r < p.Co)      // as epilogue_frag: fp16, then + residual
-                        v = (float)(half_t)v + (float)p.res[opix(m) * p.res_cpitch + p.res_coff + nx + r];
-                    const float f = (float)(half_t)v;
-                    d0 += f * (float)(half_t)p.fuse_w[nx + r];
-                    d1 += f * (float)(half_t)p.fuse_w[p.Npad + nx + r];
-                    d2 += f * (float)(half_t)p.fuse_w[2 * p.Npad + nx + r];
+                    for (int r = 0; r < 4; ++r) {
+                        float v = accx[i][r] + (p.bias ? p.bias[nx + r] : 0.f);
+                        if (eflags & HAVC_F_RELU_PRE) v = v > 0.f ? v : (leaky ? v * p.f2 : 0.f);
+                        if ((eflags & HAVC_F_RESIDUAL) && m < p.M && nx + r < p.Co)      // as epilogue_frag: fp16, then + residual
+                            v = (float)(half_t)v + (float)p.res[opix(m) * p.res_cpitch + p.res_coff + nx + r];
+                        const float f = (float)(half_t)v;
+                        d0 += f * (float)(half_t)p.fuse_w[nx + r];
+                        d1 += f * (float)(half_t)p.fuse_w[p.Npad + nx + r];
+                        d2 += f * (float)(half_t)p.fuse_w[2 * p.Npad + nx + r];
+                    }
+                    dx[i][0] = d0; dx[i][1] = d1; dx[i][2] = d2;
                 }
                 float* q = part + (4 * BM + pl) * 3;
-                q[0] = d0; q[1] = d1; q[2] = d2;
+                q[0] = dx[i][0]; q[1] = dx[i][1]; q[2] = dx[i][2];
             }
         }
         __syncthreads();

@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(WM* WN * 64, HAVC_PIPE_WPE) conv_pipe_kernel(c
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     // ABL 40 (profiling): shader-clock stamps of the block's phases, left by wave 0 in the first output row of its tile (tools/conv_timeline.py)
-    uint64_t stamps[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t stamps[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define HAVC_STAMP(i) do { if (ABL == 40) stamps[i] = __builtin_amdgcn_s_memtime(); } while (0)
     HAVC_STAMP(0);
     const int tid = threadIdx.x;
@@ -322,7 +322,7 @@ __global__ void __launch_bounds__(WM* WN * 64, HAVC_PIPE_WPE) conv_pipe_kernel(c
             stamps[7] = hwid;
             uint64_t* d = reinterpret_cast<uint64_t*>(reinterpret_cast<half_t*>(p.y) + (int64_t)m0 * p.y_cpitch + p.y_coff + n0);
 #pragma unroll
-            for (int i = 0; i < 10; ++i) d[i] = stamps[i];
+            for (int i = 0; i < 12; ++i) d[i] = stamps[i];
         }
     }
 #undef HAVC_STAMP
