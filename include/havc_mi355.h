@@ -495,6 +495,23 @@ typedef struct havc_scene_rec {
 int havc_scene_stats(havc_ctx* ctx, const uint8_t* clip, const havc_scene_params* params, havc_scene_rec* out);
 /* the normalisation's arithmetic on one value, on the host: k = Y - min, d = max - min -> uint8(255 * (k / d)); d == 0 -> 0.  No context, no GPU. */
 int havc_scene_norm_value(int k, int d);
+/* The pixel work of the reference's SSIM / histogram scene filter (vsslib/vsscdect.py:352-495, SceneDetectFilter) on the small RGB clip
+ * [n_frames][height][width][3] (host or device pointer; a device clip is read in place), frames named by index lists in HOST memory.  Gray is cv2's
+ *   Y = (4899 R + 9617 G + 1868 B + 8192) >> 14        COLOR_RGB2GRAY and the Y of COLOR_RGB2YUV: one expression for 8-bit input
+ * recomputed from the RGB bytes by both kernels: no gray plane is stored.  Results come back to HOST memory and the calls block until they are there.
+ * havc_scene_hist: cv2.calcHist([Y], [0], None, [256], [0, 256]) of the k frames idx[0..k) in ONE launch -> out[k][256], exact counts (a repeated frame
+ * number gets a row per mention).
+ * havc_scene_ssim: skimage.metrics.structural_similarity(Y_a, Y_b, full=False) of the m pairs (pairs[2 i], pairs[2 i + 1]) in ONE launch (+ one small
+ * reduction launch) -> out[m]: win_size 7, uniform window, data_range 255, K1 0.01, K2 0.03, sample covariance (49 / 48), the mean over the
+ * (height - 6) x (width - 6) window positions inside the frame.  Window sums are exact integers, the quotient is float64, partial sums are added in a
+ * fixed order without floating-point atomics: bit-identical from run to run, and a pair's value does not depend on the rest of the list.
+ * A frame number outside the clip, an empty list, and for havc_scene_ssim a frame below 7 x 7 (skimage raises there): HAVC_E_INVALID, nothing runs. */
+int havc_scene_hist(havc_ctx* ctx, const uint8_t* clip, int n_frames, int width, int height, const int* idx, int k, uint32_t* out);
+int havc_scene_ssim(havc_ctx* ctx, const uint8_t* clip, int n_frames, int width, int height, const int* pairs, int m, double* out);
+/* the two kernels' arithmetic on the host, no context, no GPU: the gray value of one pixel, and S of one window position from its integer sums
+ * (sum x, sum y, sum x^2, sum y^2, sum x * y over the 49 samples) */
+int havc_scene_gray(int r, int g, int b);
+double havc_scene_ssim_value(int sx, int sy, int sxx, int syy, int sxy);
 /* HAVC_bw_tune (vsdeoldify/__init__.py:1266-1339) and HAVC_auto_levels (:3150-3179 -> havc_utils.py:785-833) on a whole clip [n_frames][height][width][3]:
  * rgb_balance (havc_utils.py:1087-1145; with balance != 0) and rgb_equalizer (:836-1075), methods 0-3, in two launches (three with balance) that hand their
  * per-frame results on in device memory.

@@ -155,6 +155,10 @@ SYMBOLS = [
     ("havc_tile_reconstruct", _I, [_P, _P, _P, _P, _P]),
     ("havc_scene_stats", _I, [_P, _P, _P, _P]),
     ("havc_scene_norm_value", _I, [_I, _I]),
+    ("havc_scene_hist", _I, [_P, _P, _I, _I, _I, _P, _I, _P]),
+    ("havc_scene_ssim", _I, [_P, _P, _I, _I, _I, _P, _I, _P]),
+    ("havc_scene_gray", _I, [_I, _I, _I]),
+    ("havc_scene_ssim_value", _D, [_I, _I, _I, _I, _I]),
     ("havc_equalize_clip", _I, [_P, _P, _P, _P]),
     ("havc_equalize_frame_params", _I, [C.c_int64, _P, C.c_int64, _I, _P, _P]),
     ("havc_luma_lut", _I, [_P, _P, _P, _P, _I, _I]),

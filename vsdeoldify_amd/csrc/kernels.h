@@ -191,6 +191,13 @@ struct SceneStatsArgs {
     double tht_black, tht_white;
 };
 int launch_scene_stats(const uint8_t* clip, SceneRec* rec, SceneStatsArgs a, hipStream_t s);   // rec: n zero-filled device records
+// scfilter.hip: the pixel work of the SSIM / histogram scene filter on a clip [n][h][w][3], frames named by index lists (device memory, checked by the
+// caller).  out of launch_scene_hist: k zero-filled rows of 256 counters.  launch_scene_ssim: pairs = m x 2 frame numbers, partial = m *
+// scene_ssim_tiles(h, w) doubles of workspace, out = m doubles; h, w >= 7.
+constexpr int SCF_SSIM_TILE = 32;     // window positions per block and direction
+int scene_ssim_tiles(int h, int w, int* tiles_x = nullptr, int* tiles_y = nullptr);
+int launch_scene_hist(const uint8_t* clip, const int* idx, int k, unsigned* out, int h, int w, hipStream_t s);
+int launch_scene_ssim(const uint8_t* clip, const int* pairs, int m, double* partial, double* out, int h, int w, hipStream_t s);
 // equalize.hip: rgb_equalizer methods 0-3 (CLAHE / equalizeHist) with rgb_balance in front, on a clip [n][h][w][3] (vsdeoldify/havc_utils.py:836-1145)
 struct EqArgs {
     int n, h, w, method;          // method 0..3
@@ -252,6 +259,7 @@ void preload_tweaks();
 void preload_stabilizer();
 void preload_tiles();
 void preload_scdetect();
+void preload_scfilter();
 void preload_equalize();
 void preload_ddcolor();
 void preload_colormnet();

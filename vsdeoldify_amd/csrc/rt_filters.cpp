@@ -1,6 +1,7 @@
 // libhavc_mi355.so runtime, filters: the per-pixel filter entry points, tiles, scene statistics and equalisation.
 #include "runtime_internal.h"
 #include "scdetect_ops.h"
+#include "scfilter_ops.h"
 #include "equalize_ops.h"
 
 extern "C" {
@@ -265,6 +266,65 @@ int havc_scene_stats(havc_ctx* c, const uint8_t* clip, const havc_scene_params* 
     HIP_TRY(c, hipMemcpyAsync(out, d_rec, rb, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < a.n; ++i) out[i].min_y = 255 - out[i].min_y;       // kept as 255 - min on the device (scdetect.hip)
+    return HAVC_OK;
+}
+
+// ---- the SSIM / histogram scene filter's pixel work (scfilter.hip) ----
+int havc_scene_gray(int r, int g, int b) { return scf_gray(r & 255, g & 255, b & 255); }
+
+double havc_scene_ssim_value(int sx, int sy, int sxx, int syy, int sxy) { return scf_ssim_value(sx, sy, sxx, syy, sxy); }
+
+// what both entry points ask of their clip and index list; the list is host memory and every entry a frame of the clip, so no kernel reads outside it
+static int scene_list_check(havc_ctx* c, const char* what, const void* clip, int n_frames, int width, int height, const int* list, int count, const void* out) {
+    const std::string w(what);
+    if (!c || !clip || !list || !out) return fail(c, HAVC_E_INVALID, w + ": bad args");
+    if (n_frames <= 0 || width <= 0 || height <= 0 || (int64_t)width * height > ((int64_t)1 << 31))
+        return fail(c, HAVC_E_INVALID, w + ": bad clip size (at most 2^31 pixels per frame)");
+    if (count <= 0 || count > (1 << 24)) return fail(c, HAVC_E_INVALID, w + ": the list must have 1..2^24 entries");
+    if (is_device_ptr(list) || is_device_ptr(out)) return fail(c, HAVC_E_INVALID, w + ": the list and the result are host memory");
+    return HAVC_OK;
+}
+
+int havc_scene_hist(havc_ctx* c, const uint8_t* clip, int n_frames, int width, int height, const int* idx, int k, uint32_t* out) {
+    int rc = scene_list_check(c, "scene_hist", clip, n_frames, width, height, idx, k, out);
+    if (rc) return rc;
+    for (int i = 0; i < k; ++i)
+        if (idx[i] < 0 || idx[i] >= n_frames) return fail(c, HAVC_E_INVALID, "scene_hist: a frame number is outside the clip");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    const size_t cb = (size_t)n_frames * height * width * 3, ib = (size_t)k * sizeof(int), ob = (size_t)k * 256 * sizeof(uint32_t);
+    const uint8_t* d_clip;
+    if ((rc = stage_in(c, SCR_IN, clip, cb, &d_clip)) || (rc = ensure_scratch(c, SCR_IN2, ib)) || (rc = ensure_scratch(c, SCR_SMALL, ob))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->scratch[SCR_IN2], idx, ib, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->scratch[SCR_SMALL], 0, ob, c->stream));
+    const int e = launch_scene_hist(d_clip, (const int*)c->scratch[SCR_IN2], k, (unsigned*)c->scratch[SCR_SMALL], height, width, c->stream);
+    c->stats.launches++;
+    if (e) return hip_fail(c, (hipError_t)e, "scene_hist");
+    HIP_TRY(c, hipMemcpyAsync(out, c->scratch[SCR_SMALL], ob, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HAVC_OK;
+}
+
+int havc_scene_ssim(havc_ctx* c, const uint8_t* clip, int n_frames, int width, int height, const int* pairs, int m, double* out) {
+    int rc = scene_list_check(c, "scene_ssim", clip, n_frames, width, height, pairs, m, out);
+    if (rc) return rc;
+    if (width < 7 || height < 7) return fail(c, HAVC_E_INVALID, "scene_ssim: the 7 x 7 window needs frames of at least 7 x 7");
+    for (int i = 0; i < 2 * m; ++i)
+        if (pairs[i] < 0 || pairs[i] >= n_frames) return fail(c, HAVC_E_INVALID, "scene_ssim: a frame number is outside the clip");
+    const int64_t tiles = scene_ssim_tiles(height, width);
+    if ((int64_t)m * tiles > 0x7FFFFFFFll) return fail(c, HAVC_E_INVALID, "scene_ssim: too many pairs for one launch at this size");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    const size_t cb = (size_t)n_frames * height * width * 3, pb = (size_t)m * 2 * sizeof(int), ob = (size_t)m * sizeof(double);
+    const uint8_t* d_clip;
+    if ((rc = stage_in(c, SCR_IN, clip, cb, &d_clip)) || (rc = ensure_scratch(c, SCR_IN2, pb)) || (rc = ensure_scratch(c, SCR_SMALL, ob * (size_t)(1 + tiles)))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->scratch[SCR_IN2], pairs, pb, hipMemcpyHostToDevice, c->stream));
+    double* d_out = (double*)c->scratch[SCR_SMALL];                          // m results, then m * tiles partials
+    const int e = launch_scene_ssim(d_clip, (const int*)c->scratch[SCR_IN2], m, d_out + m, d_out, height, width, c->stream);
+    c->stats.launches += 2;
+    if (e) return hip_fail(c, (hipError_t)e, "scene_ssim");
+    HIP_TRY(c, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return HAVC_OK;
 }
 

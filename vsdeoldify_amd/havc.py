@@ -7,6 +7,8 @@
     HAVC_deepex      vsdeoldify/__init__.py:1421-1735     (ex_model 0 = ColorMNet, method 0; `scenes=` is the SceneInfo the reference reads off clip_ref's props)
     HAVC_bw_tune     vsdeoldify/__init__.py:1266-1339     HAVC_auto_levels vsdeoldify/__init__.py:3150-3179   (methods 0-3: CLAHE / equalizeHist; equalize.py)
     HAVC_DeepRemaster vsdeoldify/__init__.py:2689-2735    (mode 0: reference stills from a directory; remaster_render.RemasterRender; fast mode only)
+    HAVC_extract_reference_frames vsdeoldify/__init__.py:3272-3351   (sc_algo 0: SceneDetect + the SSIM / histogram post-filter, then ref_nnnnnn.jpg|png on disk)
+    HAVC_export_reference_frames  vsdeoldify/__init__.py:3364-3385   HAVC_export_list_frames vsdeoldify/__init__.py:3387-3416   (the writers alone)
 
 Same names, argument lists, defaults, parameter normalisation, frame-size rule, model routing, combine dispatch
 (vsslib/mcomb.py:125-192) and error texts; a "clip" is a uint8 array [n, h, w, 3] (or one frame [h, w, 3], or a
@@ -15,7 +17,8 @@ behind `HAVC_colorizer` (models and nets are built once and reused between calls
 
 What only VapourSynth can do stays there and is REFUSED here instead of being approximated: `vs_tweak` (deoldify / ddcolor
 sat / hue other than 1 / 0, `luma_mask_sat` < 1), the temporal half of HAVC_stabilizer (`stab=True`), scene detection INSIDE HAVC_colorizer / HAVC_ddeoldify (`sc_threshold` > 0, `sc_min_freq` > 0: the reference-frame
-logic of vs_sc_ddcolor / vs_sc_tweak that hangs off it), the SSIM post-filter of HAVC_SceneDetect (`sc_tht_ssim` in (0, 1), `sc_min_int` > 1: skimage + cv2 histograms), of HAVC_deepex the exemplar models 1-3 (Deep-Exemplar, DeepRemaster: not built), methods 1-6
+logic of vs_sc_ddcolor / vs_sc_tweak that hangs off it), the SSIM post-filter INSIDE HAVC_SceneDetect (`sc_tht_ssim` in (0, 1), `sc_min_int` > 1: that refusal is pinned and
+stays; the filter itself is built and runs in HAVC_extract_reference_frames), the plugin scene detectors of HAVC_extract_reference_frames (`sc_algo` 1-3), of HAVC_deepex the exemplar models 1-3 (Deep-Exemplar, DeepRemaster: not built), methods 1-6
 (reference frames from a directory or a video), `encode_mode` 2 and `sc_framedir` / `only_ref_frames` (they write files), the parts of the DDColor
 pre-tweaks that are VapourSynth filters (`ddtweak`: bright / cont / gamma through vs_tweak, rgb_denoise, retinex), non-RGB24 formats.
 Computed here: the hue adjustment vs_sc_ddcolor applies to every DDColor frame (default "300:360|0.8,0.1") and the luma-constrained
@@ -32,6 +35,11 @@ contract; none of it can be executed where the fixtures are made
     Spline36 on the gray plane -> the library's Spline64 on the RGB clip, at the reference's size; `misc.SCDetect` on the default path (threshold >= 0.10,
     offset 1) -> prev_n = diff(n - 1, n) > threshold, prev_0 = 1, next_n = prev_(n + 1), next_last = 1.  The custom detector (threshold < 0.10 or offset > 1) and
     the black / white filter are the reference's Python, restated and pinned by tests/golden/scdetect.npz.
+  * the SSIM / histogram post-filter (HAVC_extract_reference_frames; scdetect.py has the details): skimage's structural_similarity -> its published formula
+    over exact integer 7 x 7 window sums, float64 quotient; cv2's gray -> (4899 R + 9617 G + 1868 B + 8192) >> 14; cv2.calcHist -> exact counts;
+    cv2.normalize + compareHist(HELLINGER) (float32 histograms there) -> OpenCV's published definition in float64; the zimg resize of the RGB clip in
+    front of the filter -> the library's Spline64.  None of skimage, cv2 or zimg can be executed where the fixtures are made.  The selector on top of
+    the two scores is the reference's Python, restated and pinned by tests/golden/scfilter.npz.
   * HAVC_bw_tune / HAVC_auto_levels (vsdeoldify_amd/equalize.py has the details): `std.Levels` -> a 256-entry table, `resize.Bicubic(range_in_s, range_s)` at
     unchanged size -> a per-sample range scale rounded to nearest (the reference applies both, on the way in and on the way out: so does this), `std.Merge` ->
     a + (((b - a) * w15 + 16384) >> 15), `std.PlaneStats` -> sum / (n_pixels * 255), `std.Expr "x g *"` -> a float32 product rounded half to even; cv2's CLAHE
@@ -664,7 +672,8 @@ def HAVC_SceneDetect(clip, sc_threshold=0.10, sc_tht_offset=1, sc_tht_ssim=0.0, 
     `scdetect.SceneInfo` (scene_change_prev / scene_change_next / sc_luma / sc_ratio per frame + sc_threshold / sc_frequency).  The per-frame statistics
     are ONE launch over the clip (havc_scene_stats; two with sc_normalize); a DeviceImage stays in HBM and only the per-frame records come back.  The
     decision is scdetect.scene_flags, on the host.  sc_debug is accepted and ignored.  luma_range ("limited" / "full") picks the gray conversion's
-    coefficients (module docstring).  The SSIM post-filter is refused before anything is enqueued."""
+    coefficients (module docstring).  The SSIM post-filter is refused HERE before anything is enqueued (tests/test_scdetect_host.py pins that); it is built as
+    scdetect.scene_detect_filtered and runs in HAVC_extract_reference_frames."""
     from . import scdetect
     if clip is None or not (is_device(clip) or isinstance(clip, np.ndarray)):
         raise HAVCError("HAVC_SceneDetect: this is not a clip")
@@ -678,6 +687,141 @@ def HAVC_SceneDetect(clip, sc_threshold=0.10, sc_tht_offset=1, sc_tht_ssim=0.0, 
     return scdetect.scene_detect(ctx, clip, threshold=sc_threshold, frequency=sc_min_freq, sc_tht_filter=sc_tht_ssim, min_length=sc_min_int,
                                  tht_white=sc_tht_white, tht_black=sc_tht_black, frame_norm=sc_normalize, tht_offset=sc_tht_offset,
                                  coeffs=scdetect.LUMA_LIMITED if luma_range == "limited" else scdetect.LUMA_FULL)
+
+
+# ---- HAVC_extract_reference_frames / HAVC_export_reference_frames / HAVC_export_list_frames (vsdeoldify/__init__.py:3272-3416 -> vsslib/vsutils.py:147-233) ----
+DEF_EXPORT_FORMAT, DEF_JPG_QUALITY = 'jpg', 95                                                     # vsslib/constants.py:58-59
+
+
+def _export_checks(what, clip, sc_framedir, ref_ext):
+    """what touches no pixel, before a context exists -> the extension as the writer uses it (vsutils.py:150: lower case).  Pillow picks the format by the
+    file name (everything but "jpg" goes through a bare img.save): an extension it does not know is refused here, where the reference would fail on its
+    first frame."""
+    from PIL import Image
+    if clip is None or not (is_device(clip) or isinstance(clip, np.ndarray)):
+        raise HAVCError(f"{what}: this is not a clip")
+    if not isinstance(sc_framedir, (str, os.PathLike)):
+        raise HAVCError(f"{what}: sc_framedir must be a directory name")
+    ext = str(ref_ext).lower()
+    if "." + ext not in Image.registered_extensions():
+        raise HAVCError(f"{what}: Pillow knows no image format for the extension '{ref_ext}'")
+    return ext
+
+
+def _save_ref_frames(clip, frames, numbers, sc_framedir, ext, ref_jpg_quality, ref_override):
+    """save_sc_frame (vsutils.py:154-175 / :198-218): frame frames[i] of the clip -> sc_framedir/ref_{numbers[i]:06d}.ext; with ref_override off an
+    existing file is left alone.  A DeviceImage clip hands over the listed frames only, one at a time.  -> the paths written"""
+    from PIL import Image
+    written = []
+    for f, num in zip(frames, numbers):
+        path = os.path.join(sc_framedir, f"ref_{num:06d}.{ext}")
+        if not ref_override and os.path.exists(path):
+            continue
+        img = Image.fromarray(clip.frame(f).numpy() if is_device(clip) else np.ascontiguousarray(clip[f]), 'RGB')
+        if ext == "jpg":
+            img.save(path, subsampling=0, quality=ref_jpg_quality)
+        else:
+            img.save(path)
+        written.append(path)
+    return written
+
+
+def _export_scene_frames(clip, scenes, sc_framedir, ref_offset, ext, ref_jpg_quality, ref_override, sequence):
+    """vs_sc_export_frames (vsutils.py:147-182): frame 0 and every frame with _SceneChangePrev == 1, named by its number + ref_offset, or with `sequence` by a
+    counter from 0 (no offset there) that also counts a frame ref_override leaves alone"""
+    frames = [i for i in range(clip.shape[0]) if i == 0 or scenes.scene_change_prev[i] == 1]
+    numbers = list(range(len(frames))) if sequence else [i + ref_offset for i in frames]
+    return _save_ref_frames(clip, frames, numbers, sc_framedir, ext, ref_jpg_quality, ref_override)
+
+
+def HAVC_extract_reference_frames(clip, sc_threshold=0.10, sc_tht_offset=1, sc_tht_ssim=0.0, sc_min_int=1, sc_min_freq=0, sc_framedir="./", sc_sequence=False,
+                                  sc_normalize=False, ref_offset=0, sc_tht_white=0.70, sc_tht_black=0.10, ref_ext=DEF_EXPORT_FORMAT,
+                                  ref_jpg_quality=DEF_JPG_QUALITY, ref_override=True, sc_algo=0, sc_debug=False, *, device_index=0, luma_range="limited",
+                                  debug=None):
+    """vsdeoldify/__init__.py:3272-3351: detect the scene changes of a clip and write frame 0 and every flagged frame to sc_framedir as ref_nnnnnn.jpg|png --
+    the stills HAVC_DeepRemaster(ref_dir=...) reads back once they are coloured.  sc_algo 0 only (SceneDetect + the SSIM filter); the other algorithms are
+    VapourSynth plugins.  With 0 < sc_tht_ssim < 1 or sc_min_int > 1 the detection is scdetect.scene_detect_filtered (the SSIM / histogram post-filter: two
+    launches over the candidates, csrc/scfilter.hip, the decision on the host), otherwise scdetect.scene_detect as in HAVC_SceneDetect.  The reference returns
+    the clip with its props; arrays carry none: the `scdetect.SceneInfo` comes back.  A DeviceImage clip stays in HBM, only the written frames leave it.
+    sc_debug is accepted and ignored; `debug` (a dict) receives "written" (the paths) and, with the filter, scene_detect_filtered's launch counts and the
+    per-candidate "scores" {frame: (ssim_score, hist_score)}."""
+    from . import scdetect
+    what = "HAVC_extract_reference_frames"
+    ext = _export_checks(what, clip, sc_framedir, ref_ext)
+    if luma_range not in ("limited", "full"):
+        raise HAVCError(f"{what}: luma_range must be 'limited' or 'full'")
+    if sc_algo in (1, 2, 3):
+        plugin = {1: "SceneDetectEdges needs the TCanny and akarin plugins", 2: "vs_sc_xvid needs the SCXvid plugin", 3: "vs_mv_sc_detect needs the MVTools plugin"}
+        raise NotImplementedError(f"{what}: sc_algo = {sc_algo} is not built ({plugin[sc_algo]}): only sc_algo = 0 (SceneDetect + SSIM filter) is")
+    if sc_algo != 0:
+        raise HAVCError(f"{what}: sc_algo must be in range [0-3]")
+    clip, _ = _as_clip(clip)
+    n, h, w, _ = clip.shape
+    early = (sc_threshold == 0 and sc_min_freq == 0) or sc_min_freq == 1 or (sc_threshold == 0 and sc_min_freq > 1)      # vsscdect.py:50, 71: no pixel is read
+    filtered = not early and scdetect.filter_active(sc_tht_ssim, sc_min_int)
+    if filtered and sc_tht_ssim != 1 and min(scdetect.resize_min_hw(w, h)) < scdetect.SSIM_WIN:
+        raise HAVCError(f"{what}: the SSIM filter's 7 x 7 window needs frames of at least 7 x 7 (skimage raises below), not {h} x {w}")
+    os.makedirs(sc_framedir, exist_ok=True)
+    ctx = None if early else (clip.ctx if is_device(clip) else get_context(device_index))
+    kw = dict(threshold=sc_threshold, frequency=sc_min_freq, sc_tht_filter=sc_tht_ssim, min_length=sc_min_int, tht_white=sc_tht_white, tht_black=sc_tht_black,
+              frame_norm=sc_normalize, tht_offset=sc_tht_offset, coeffs=scdetect.LUMA_LIMITED if luma_range == "limited" else scdetect.LUMA_FULL)
+    if filtered:
+        scenes = scdetect.scene_detect_filtered(ctx, clip, debug=debug, **kw)
+    else:
+        scenes = scdetect.scene_detect(ctx, clip, **dict(kw, min_length=1))                     # sc_min_int clamps to 1 here, or an early return ignores it
+    written = _export_scene_frames(clip, scenes, sc_framedir, ref_offset, ext, ref_jpg_quality, ref_override, sc_sequence)
+    if debug is not None:
+        debug["written"] = written
+    return scenes
+
+
+def HAVC_export_reference_frames(clip, sc_framedir="./", ref_offset=0, ref_ext=DEF_EXPORT_FORMAT, ref_jpg_quality=DEF_JPG_QUALITY, ref_override=True, *,
+                                 scenes=None, debug=None):
+    """vsdeoldify/__init__.py:3364-3385: the writer of HAVC_extract_reference_frames on scene changes that are already known.  The reference reads them off
+    the clip's frame props; arrays carry none: `scenes` is the SceneInfo (HAVC_SceneDetect's or HAVC_extract_reference_frames' result for this clip).
+    -> the clip, as it came."""
+    what = "HAVC_export_reference_frames"
+    ext = _export_checks(what, clip, sc_framedir, ref_ext)
+    c, _ = _as_clip(clip)
+    if scenes is None or len(scenes.scene_change_prev) != c.shape[0]:
+        raise HAVCError(f"{what}: scenes= must be the SceneInfo of this clip (the reference reads _SceneChangePrev off every frame)")
+    os.makedirs(sc_framedir, exist_ok=True)
+    written = _export_scene_frames(c, scenes, sc_framedir, ref_offset, ext, ref_jpg_quality, ref_override, False)
+    if debug is not None:
+        debug["written"] = written
+    return clip
+
+
+def HAVC_export_list_frames(clip, sc_framedir="./", ref_list=None, offset=0, ref_ext=DEF_EXPORT_FORMAT, ref_jpg_quality=DEF_JPG_QUALITY, ref_override=True,
+                            fast_extract=True, *, debug=None):
+    """vsdeoldify/__init__.py:3387-3416 -> vs_list_export_frames (vsutils.py:185-233): write the listed frames as ref_nnnnnn.  A list of ONE number k means
+    every k-th frame from 0; otherwise the list is sorted and its duplicates dropped.  offset > 0 is added to every number, and the frame that is written
+    (and named) is the one at number + offset.  fast_extract picks the frames directly and refuses a number outside the clip; without it the whole clip is
+    walked and such a number is never met.  None or an empty list: nothing happens.  -> the clip, as it came."""
+    what = "HAVC_export_list_frames"
+    if ref_list is None or len(ref_list) < 1:
+        return clip
+    ext = _export_checks(what, clip, sc_framedir, ref_ext)
+    c, _ = _as_clip(clip)
+    n = c.shape[0]
+    if len(ref_list) == 1:
+        if int(ref_list[0]) < 1:
+            raise HAVCError(f"{what}: a one-element ref_list is a step and must be positive")
+        frames = list(range(0, n, int(ref_list[0])))
+    else:
+        frames = sorted(set(int(f) for f in ref_list))
+    if offset > 0:
+        frames = [f + offset for f in frames]
+    if fast_extract:
+        if any(f < 0 or f > n - 1 for f in frames):
+            raise HAVCError("Frame numbers in list must be in range [0, clip.num_frames - 1]")                      # vsutils.py:133-134
+    else:
+        frames = [f for f in frames if 0 <= f < n]
+    os.makedirs(sc_framedir, exist_ok=True)
+    written = _save_ref_frames(c, frames, frames, sc_framedir, ext, ref_jpg_quality, ref_override)
+    if debug is not None:
+        debug["written"] = written
+    return clip
 
 
 # ---- HAVC_deepex (vsdeoldify/__init__.py:1421-1735), ex_model 0 = ColorMNet, method 0 = reference frames from clip_ref -------------------------------------
