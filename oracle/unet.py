@@ -144,3 +144,16 @@ def unet_forward(sd, x0, arch="wide", return_presigmoid=False):
     if return_presigmoid:
         return y
     return torch.sigmoid(y) * 6.0 - 3.0                     # layers.12 SigmoidRange(-3,3) (fastai/layers.py:163-170)
+
+
+def self_attention_f64(x, f, g, h, gamma):
+    """fastai SelfAttention (the layer self_attention above restates; fastai/layers.py:81-96) on ONE frame in plain float64 numpy, after the three 1x1 convs:
+    x [N][C], f = query(x) [N][d], g = key(x) [N][d], h = value(x) [N][C] -> (out [N][C], A [N][C]).
+    s[j][i] = g_j . f_i (no 1/sqrt(d)), p = softmax over i, out_j = gamma sum_i p[j][i] h_i + x_j;  A_j = sum_i p[j][i] |h_i|, the
+    attention-weighted mean of |h| that the error bound of tests/deoldify_ops_util.py is made of."""
+    import numpy as np
+    x, f, g, h = (np.asarray(a, np.float64) for a in (x, f, g, h))
+    s = g @ f.T
+    p = np.exp(s - s.max(axis=1, keepdims=True))
+    p /= p.sum(axis=1, keepdims=True)
+    return float(gamma) * (p @ h) + x, p @ np.abs(h)

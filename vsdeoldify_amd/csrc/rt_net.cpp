@@ -22,6 +22,21 @@ int run_op(havc_net* n, const havc_op& op, int batch) {
     };
     if (timed) if (int rc = open_tag_pair()) return rc;
     const bool precise = op.flags & HAVC_F_PRECISE;         // fast / precise twins with one parameter list: pick the function, write the call once
+    // Dense-frame ops (MAXPOOL, BLUR_RESIZE, AFFINE, COPY_CH, PREP_RGB8, fast ATTENTION): their kernels place frame b at b x rows x pitch.  That is the
+    // buffer's own frame only where the view fills it; a view that covers part of its buffer's frame (the h x w patch rows of a token buffer whose
+    // frame also holds a class row) runs one launch per frame, each pointer advanced by its buffer's own frame size -- as the conv op does.
+    auto fills = [&](int id, uint64_t elems) { return (uint64_t)n->bufdesc[id].elems_per_frame == elems; };
+    auto frame_at = [&](int id, int f) { return (char*)bufptr(n, id) + (uint64_t)f * n->bufdesc[id].elems_per_frame * n->bufdesc[id].elem_bytes; };
+    auto by_frame = [&](bool dense, auto&& launch) -> int {     // launch(first frame, frames) -> hipError
+        if (dense || batch == 1) return launch(0, batch);
+        int rc = 0;
+        for (int f = 0; f < batch && rc == 0; ++f) {
+            rc = launch(f, 1);
+            if (f > 0) c->stats.launches += 1;
+        }
+        return rc;
+    };
+    const uint64_t src_rows = (uint64_t)op.Hi * op.Wi, dst_rows = (uint64_t)op.Ho * op.Wo;
     switch (op.type) {
         case HAVC_OP_CONV: {
             ConvArgs a{};
@@ -173,22 +188,29 @@ int run_op(havc_net* n, const havc_op& op, int batch) {
             break;
         }
         case HAVC_OP_MAXPOOL:
-            e = (precise ? launch_maxpool3x3s2_p : launch_maxpool3x3s2)((const half_t*)bufptr(n, op.src), (half_t*)bufptr(n, op.dst), batch, op.Hi, op.Wi, op.Ho,
-                                                                        op.Wo, op.Ci, op.src_cpitch, op.src_coff, op.dst_cpitch, op.dst_coff, s);
+            e = by_frame(fills(op.src, src_rows * op.src_cpitch) && fills(op.dst, dst_rows * op.dst_cpitch), [&](int f, int nb) {
+                return (precise ? launch_maxpool3x3s2_p : launch_maxpool3x3s2)((const half_t*)frame_at(op.src, f), (half_t*)frame_at(op.dst, f), nb, op.Hi, op.Wi,
+                                                                               op.Ho, op.Wo, op.Ci, op.src_cpitch, op.src_coff, op.dst_cpitch, op.dst_coff, s);
+            });
             break;
         case HAVC_OP_BLUR_RESIZE:
-            e = (precise ? launch_blur_resize_p : launch_blur_resize)((const half_t*)bufptr(n, op.src), (half_t*)bufptr(n, op.dst), batch, op.Hi, op.Wi, op.Ho,
-                                                                      op.Wo, op.Ci, op.src_cpitch, op.src_coff, op.dst_cpitch, op.dst_coff, s);
+            e = by_frame(fills(op.src, src_rows * op.src_cpitch) && fills(op.dst, dst_rows * op.dst_cpitch), [&](int f, int nb) {
+                return (precise ? launch_blur_resize_p : launch_blur_resize)((const half_t*)frame_at(op.src, f), (half_t*)frame_at(op.dst, f), nb, op.Hi, op.Wi,
+                                                                             op.Ho, op.Wo, op.Ci, op.src_cpitch, op.src_coff, op.dst_cpitch, op.dst_coff, s);
+            });
             break;
         case HAVC_OP_AFFINE:
-            e = (precise ? launch_affine_p : launch_affine)((const half_t*)bufptr(n, op.src), (half_t*)bufptr(n, op.dst), wptr<float>(n, op.scale_off),
-                                                            wptr<float>(n, op.shift_off), (op.flags & HAVC_F_RELU_POST) ? 1 : 0,
-                                                            (int64_t)batch * op.Hi * op.Wi, op.Ci, op.src_cpitch, op.src_coff, op.dst_cpitch,
-                                                            op.dst_coff, s);
+            e = by_frame(fills(op.src, src_rows * op.src_cpitch) && fills(op.dst, src_rows * op.dst_cpitch), [&](int f, int nb) {
+                return (precise ? launch_affine_p : launch_affine)((const half_t*)frame_at(op.src, f), (half_t*)frame_at(op.dst, f), wptr<float>(n, op.scale_off),
+                                                                   wptr<float>(n, op.shift_off), (op.flags & HAVC_F_RELU_POST) ? 1 : 0,
+                                                                   (int64_t)nb * op.Hi * op.Wi, op.Ci, op.src_cpitch, op.src_coff, op.dst_cpitch, op.dst_coff, s);
+            });
             break;
         case HAVC_OP_COPY_CH:
-            e = launch_copy_ch((const half_t*)bufptr(n, op.src), (half_t*)bufptr(n, op.dst), (int64_t)batch * op.Hi * op.Wi,
-                               op.Ci, op.src_cpitch, op.src_coff, op.dst_cpitch, op.dst_coff, s);
+            e = by_frame(fills(op.src, src_rows * op.src_cpitch) && fills(op.dst, src_rows * op.dst_cpitch), [&](int f, int nb) {
+                return launch_copy_ch((const half_t*)frame_at(op.src, f), (half_t*)frame_at(op.dst, f), (int64_t)nb * op.Hi * op.Wi, op.Ci, op.src_cpitch,
+                                      op.src_coff, op.dst_cpitch, op.dst_coff, s);
+            });
             break;
         case HAVC_OP_ATTENTION:
             if (op.flags & HAVC_F_PRECISE) {
@@ -218,20 +240,40 @@ int run_op(havc_net* n, const havc_op& op, int batch) {
                 c->stats.launches += 1;
                 break;
             }
-            e = launch_attention((const half_t*)bufptr(n, op.src2), op.res_cpitch, op.res_coff, op.res_coff + op.aux0,
-                                 op.aux0, (const half_t*)bufptr(n, op.aux1), op.Ci, op.Kc, (const half_t*)bufptr(n, op.src),
-                                 op.src_cpitch, op.src_coff, (half_t*)bufptr(n, op.dst), op.dst_cpitch, op.dst_coff, batch,
-                                 op.Hi * op.Wi, op.f0, s);
+            {
+                // fast form: qk = [N][res_cpitch] with f at res_coff and g at res_coff + d, aux1 = V^T [C][Kc], x / y = C-channel views.  Everything the
+                // kernels take on trust is checked here, before any launch.
+                const int d = op.aux0, C = op.Ci;
+                const uint64_t N = src_rows;
+                if (d != 32 && d != 64 && d != 96) return fail(c, HAVC_E_INVALID, "attention op: d (aux0) must be 32, 64 or 96");
+                if (C < 128 || (C & 127)) return fail(c, HAVC_E_INVALID, "attention op: C % 128 == 0");
+                if (N < 1 || op.Kc < 64 || (op.Kc & 63) || (uint64_t)op.Kc < N) return fail(c, HAVC_E_INVALID, "attention op: value pitch Kc % 64 == 0, Kc >= N");
+                if (op.src2 < 0 || op.res_coff < 0 || op.src_coff < 0 || op.dst_coff < 0 || op.res_coff + 2 * d > op.res_cpitch || op.src_coff + C > op.src_cpitch ||
+                    op.dst_coff + C > op.dst_cpitch || ((op.res_coff | op.res_cpitch | op.src_coff | op.src_cpitch | op.dst_coff | op.dst_cpitch) & 7))
+                    return fail(c, HAVC_E_INVALID, "attention op: views inside their pixel rows (res_coff + 2 d <= res_cpitch, coff + C <= cpitch), in units of 8 channels");
+                const havc_buf &bq = n->bufdesc[op.src2], &bv = n->bufdesc[op.aux1], &bx = n->bufdesc[op.src], &by = n->bufdesc[op.dst];
+                if (bq.elem_bytes != 2 || bv.elem_bytes != 2 || bx.elem_bytes != 2 || by.elem_bytes != 2 || (uint64_t)bq.elems_per_frame < N * op.res_cpitch ||
+                    (uint64_t)bx.elems_per_frame < N * op.src_cpitch || (uint64_t)by.elems_per_frame < N * op.dst_cpitch ||
+                    (uint64_t)bv.elems_per_frame < (uint64_t)C * op.Kc)
+                    return fail(c, HAVC_E_INVALID, "attention op: fp16 buffers of N x pitch elements per frame, V^T of C x Kc");
+                const bool dense = fills(op.src2, N * op.res_cpitch) && fills(op.aux1, (uint64_t)C * op.Kc) && fills(op.src, N * op.src_cpitch) &&
+                                   fills(op.dst, N * op.dst_cpitch);
+                e = by_frame(dense, [&](int f, int nb) {
+                    return launch_attention((const half_t*)frame_at(op.src2, f), op.res_cpitch, op.res_coff, op.res_coff + d, d, (const half_t*)frame_at(op.aux1, f), C,
+                                            op.Kc, (const half_t*)frame_at(op.src, f), op.src_cpitch, op.src_coff, (half_t*)frame_at(op.dst, f), op.dst_cpitch,
+                                            op.dst_coff, nb, (int)N, op.f0, s);
+                });
+            }
             break;
         case HAVC_OP_PREP_RGB8:
-            if (op.flags & HAVC_F_PRECISE) {
-                e = launch_prep_rgb8_p((const uint8_t*)bufptr(n, op.src), (half_t*)bufptr(n, op.dst), op.dst_cpitch, op.dst_coff,
-                                       op.src2 >= 0 ? (half_t*)bufptr(n, op.src2) : nullptr, op.res_cpitch, op.res_coff, (int64_t)batch * op.Hi * op.Wi, s);
-                break;
-            }
-            e = launch_prep_rgb8((const uint8_t*)bufptr(n, op.src), (half_t*)bufptr(n, op.dst), op.dst_cpitch, op.dst_coff,
-                                 op.src2 >= 0 ? (half_t*)bufptr(n, op.src2) : nullptr, op.res_cpitch, op.res_coff,
-                                 (int64_t)batch * op.Hi * op.Wi, s, op.aux0 > 0 && op.res_coff + 8 + op.aux0 <= op.res_cpitch ? op.aux0 : 0);
+            e = by_frame(fills(op.src, src_rows * 3) && fills(op.dst, src_rows * op.dst_cpitch) && (op.src2 < 0 || fills(op.src2, src_rows * op.res_cpitch)),
+                         [&](int f, int nb) {
+                const uint8_t* rgb = (const uint8_t*)frame_at(op.src, f);
+                half_t *y0 = (half_t*)frame_at(op.dst, f), *y1 = op.src2 >= 0 ? (half_t*)frame_at(op.src2, f) : nullptr;
+                if (precise) return launch_prep_rgb8_p(rgb, y0, op.dst_cpitch, op.dst_coff, y1, op.res_cpitch, op.res_coff, (int64_t)nb * op.Hi * op.Wi, s);
+                return launch_prep_rgb8(rgb, y0, op.dst_cpitch, op.dst_coff, y1, op.res_cpitch, op.res_coff, (int64_t)nb * op.Hi * op.Wi, s,
+                                        op.aux0 > 0 && op.res_coff + 8 + op.aux0 <= op.res_cpitch ? op.aux0 : 0);
+            });
             break;
         case HAVC_OP_SUBSAMPLE2:
             e = (precise ? launch_subsample2_p : launch_subsample2)((const half_t*)bufptr(n, op.src), (half_t*)bufptr(n, op.dst), batch, op.Ho, op.Wo, op.Hi, op.Wi,
