@@ -552,6 +552,33 @@ int havc_luma_lut(havc_ctx* ctx, const uint8_t* img, const uint8_t* lut256, uint
  * returns the mask replicated to RGB. */
 int havc_restore_color_gradient(havc_ctx* ctx, const uint8_t* img_color, const uint8_t* img_gray, uint8_t* out, int width, int height,
                                 double sat, int tht, double weight, double alpha, int algo, int return_mask);
+/* HAVC_recover_clip_color (vsdeoldify/__init__.py:2956-2992) = ChromaRetentionMerge (vsslib/mcomb.py:450-516) on a whole clip [n_frames][height][width][3]:
+ * the reference's two per-frame selectors in two launches that hand the per-frame luma sums on in device memory (no host round trip).
+ *   launch 1  per frame of `gray`: the sum of cv2's Y (what havc_image_luma sums), integer partial sums added with 64-bit integer atomics
+ *   launch 2  f_luma = round(sum / n_pixels / 255, 6) in float64 (numpy's round: multiply, rint, divide); a frame outside
+ *             DEF_STANDARD_DARK (0.22) <= f_luma <= DEF_STANDARD_BRIGHT (0.78) has its weight (and alpha) overridden, then per pixel
+ *   binary_mask == 0  vs_sc_recover_gradient_color (vsslib/vsfilters.py:391-412): outside the band weight = min(weight, -0.5), alpha = max(alpha, 4.0);
+ *                     the pixel is havc_restore_color_gradient's above, the same code (weight > 0 merges towards the colour frame, < 0 towards the gray one)
+ *   binary_mask != 0  vs_sc_recover_clip_color (vsfilters.py:327-351) -> restore_color (vsslib/restcolor.py:38-83) with tht_scen = 1.0, hue_adjust 'none':
+ *                     a frame whose clip index first_frame + i is below 15 comes back as it went in (before everything else, return_mask included); outside
+ *                     the band weight = min(weight, -0.8); the saturation product runs for every sat (sat == 1 too); mask = 255 where S_gray < tht, else 0
+ *                     (integer compare), np_image_mask_merge; weight > 0 merges towards the GRAY frame, < 0 towards the desaturated COLOUR frame -- the
+ *                     opposite of the gradient path.  Merges are np_weighted_merge: float64 products, clip, truncation.
+ * return_mask != 0: the mask replicated to RGB, on either path.  sat, weight and alpha are float64 and tht an integer, as the reference passes them; alpha is
+ * used as given (ChromaRetentionMerge clamps it to [1, 10] in front: the caller's step). */
+typedef struct havc_recover_params {
+    int width, height, n_frames;  /* at most 2^31 pixels per frame */
+    int first_frame;              /* >= 0: clip index of the first frame (binary path: `if n < 15`) */
+    double sat;
+    int tht;
+    int algo;                     /* 0..2: mask algorithm of the gradient path (restcolor.py:137-217); checked on both paths */
+    double weight, alpha;
+    int binary_mask, return_mask;
+} havc_recover_params;
+/* gray: the clip to repair; color: the colour donor; out: the result, which must alias neither input.  Host or device pointers like every filter here; device
+ * operands: the call only enqueues.  Integer sums and stated float sequences throughout: the bytes are identical from run to run.  algo outside 0..2,
+ * n_frames < 1, a non-positive size, first_frame < 0, a NULL pointer, out aliasing an input: HAVC_E_INVALID, nothing runs. */
+int havc_recover_color_clip(havc_ctx* ctx, const uint8_t* gray, const uint8_t* color, uint8_t* out, const havc_recover_params* params);
 
 /* ---- device-resident clip pipeline (bench + multi-GPU shard path) -----------------
  * One call colours n_frames 1080p-class frames that are ALREADY in HBM:

@@ -21,7 +21,8 @@ def __getattr__(name):
         return DDColorRender
     if name in ("HAVC_colorizer", "HAVC_merge", "HAVC_ddeoldify", "ddeoldify", "HAVC_stabilizer", "HAVCFrameColorizer", "HAVC_clip_slice",
                 "HAVC_clip_reconstruct", "ClipTiles", "tiled_preset_params", "HAVC_SceneDetect", "HAVC_deepex", "HAVC_auto_levels", "HAVC_bw_tune",
-                "HAVC_DeepRemaster", "HAVC_extract_reference_frames", "HAVC_export_reference_frames", "HAVC_export_list_frames"):
+                "HAVC_DeepRemaster", "HAVC_extract_reference_frames", "HAVC_export_reference_frames", "HAVC_export_list_frames",
+                "HAVC_recover_clip_color"):
         from . import havc
         return getattr(havc, name)
     if name == "RemasterRender":

@@ -87,6 +87,12 @@ class EqualizeParams(C.Structure):
                 ("balance_weight", C.c_double), ("rgb_factor", C.c_double * 3), ("lut_in", C.c_uint8 * 256), ("lut_out", C.c_uint8 * 256)]
 
 
+class RecoverParams(C.Structure):
+    """`havc_recover_params` (include/havc_mi355.h): clip size, first frame number and the arguments of ChromaRetentionMerge's selectors (havc_recover_color_clip)"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int), ("first_frame", C.c_int), ("sat", C.c_double), ("tht", C.c_int),
+                ("algo", C.c_int), ("weight", C.c_double), ("alpha", C.c_double), ("binary_mask", C.c_int), ("return_mask", C.c_int)]
+
+
 # numpy mirror of `havc_scene_rec`: one record per frame
 SCENE_REC_DTYPE = np.dtype([("sum_y", "<i8"), ("sad", "<i8"), ("sum_raw", "<i8"), ("min_y", "<i4"), ("max_y", "<i4")], align=True)
 
@@ -163,6 +169,7 @@ SYMBOLS = [
     ("havc_equalize_frame_params", _I, [C.c_int64, _P, C.c_int64, _I, _P, _P]),
     ("havc_luma_lut", _I, [_P, _P, _P, _P, _I, _I]),
     ("havc_restore_color_gradient", _I, [_P, _P, _P, _P, _I, _I, _D, _I, _D, _D, _I, _I]),
+    ("havc_recover_color_clip", _I, [_P, _P, _P, _P, _P]),
     ("havc_colorize_clip", _I, [_P, _P, _P, _F, _P, _P, _I, _I, _I]),
     ("havc_spline64_resize", _I, [_P, _P, _I, _I, _P, _I, _I, _P]),
     ("havc_spline64_resize_n", _I, [_P, _P, _I, _I, _P, _I, _I, _P, _I]),

@@ -213,6 +213,17 @@ size_t equalize_workspace_bytes(int n, int method);
 int launch_equalize(const uint8_t* src, uint8_t* dst, void* ws, EqArgs a, hipStream_t s);   // ws: see equalize.hip
 int launch_restore_color_gradient(const uint8_t* color, const uint8_t* gray, uint8_t* out, int64_t npix, double sat, int tht, double alpha,
                                   double weight, int algo, int return_mask, hipStream_t s);
+// recover.hip: HAVC_recover_clip_color / ChromaRetentionMerge on a clip [n][h][w][3] (vsslib/mcomb.py:450-516): per-frame luma sums, then the gated per-pixel
+// restore (gradient mask: restore_color_gradient; binary mask: restore_color), two launches.  sums: n slots of device memory (zeroed by the launcher).
+struct RecoverArgs {
+    int n, h, w;
+    int first_frame;              // clip index of frame 0: the binary path hands frames with index < 15 on unchanged
+    double sat, weight, alpha;
+    int tht, algo;                // algo 0..2 (gradient path)
+    int binary_mask, return_mask;
+    int luma_blocks, apply_blocks;   // blocks per frame of the two launches, set by launch_recover_color
+};
+int launch_recover_color(const uint8_t* gray, const uint8_t* color, uint8_t* out, unsigned long long* sums, RecoverArgs a, hipStream_t s);
 // separable polyphase resample of interleaved u8 RGB (tap tables from the host; Spline64 = harness stand-in
 // for zimg resize.Spline64).  orig != null fuses chroma_post_process (luma of orig, chroma of the resampled).
 int launch_resize_passes(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, int n_frames, float* tmp,
@@ -258,6 +269,7 @@ void preload_colorfilters();
 void preload_tweaks();
 void preload_stabilizer();
 void preload_tiles();
+void preload_recover();
 void preload_scdetect();
 void preload_scfilter();
 void preload_equalize();

@@ -8,6 +8,21 @@
 
 __device__ __forceinline__ int clip8i(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
+// ---- four neighbouring pixels = 12 bytes as one 96-bit access at any byte alignment (memcpy semantics; the gfx950 code object runs in unaligned access
+// mode and gets one global_load_dwordx3 / global_store_dwordx3 for each): the access pattern of tiles.hip and recover.hip ----
+__device__ __forceinline__ void load12(const uint8_t* p, int v[12]) {
+    uint32_t w[3];
+    __builtin_memcpy(w, p, 12);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) v[i] = (int)((w[i >> 2] >> ((i & 3) * 8)) & 255u);
+}
+__device__ __forceinline__ void store12(uint8_t* p, const int v[12]) {
+    uint32_t w[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 12; ++i) w[i >> 2] |= (uint32_t)v[i] << ((i & 3) * 8);
+    __builtin_memcpy(p, w, 12);
+}
+
 // ---- OpenCV RGB2YUV / YUV2RGB, 8-bit (color_yuv.simd.hpp RGB2YCrCb_i / YCrCb2RGB_i, isCrCb=false) ----
 __device__ __forceinline__ int descale14(int x) { return (x + (1 << 13)) >> 14; }
 __device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
@@ -209,4 +224,83 @@ __device__ __forceinline__ void luma_merge_pixel(int mode, double tresh, double 
         o[c] = (int)(uint8_t)(int)v;
     }
     r = o[0]; g = o[1]; b = o[2];
+}
+
+// ---- restore_color_gradient / restore_color (restcolor.py:98-217, 38-83), one pixel: the body of havc_restore_color_gradient (tweaks.hip) and of both
+// paths of havc_recover_color_clip (recover.hip) ----
+// w_np_gradient_mask (restcolor.py:137-217) from the cv2 HSV saturation s of the GRAY pixel: white (255) where it is gray.  algo 0: float64; 1, 2: float32
+// steps, then float64
+__device__ __forceinline__ int restore_gradient_mask(int s, int tht, double alpha, int algo) {
+    if (algo == 0) {
+        const double sd = (double)s;
+        const double grad = s < tht ? 2.0 * sd / alpha - (double)tht : 2.0 * (sd - (double)tht) * alpha;
+        double m = 255.0 - (double)tht - grad;
+        m = m < 0.0 ? 0.0 : (m > 255.0 ? 255.0 : m);
+        return (int)m;
+    }
+    const int t = tht < 0 ? 0 : (tht > 255 ? 255 : tht);
+    if (t == 0) return 0;
+    const float sf = (float)s;
+    double mn;
+    if (algo == 1) {
+        const float max_s = (float)min(2 * t, 200);
+        const float sc = fminf(fmaxf(sf, 0.f), max_s);
+        mn = (double)powf(1.0f - sc / max_s, (float)alpha);
+    } else {
+        const float s_rel = fminf(fmaxf(sf / (float)t, 0.f), 2.f);
+        mn = exp((double)((float)(-alpha) * s_rel) * 0.6931471805599453);
+        if (sf >= (float)(2 * t)) mn = 0.0;
+    }
+    double m = mn * 255.0;
+    m = m < 0.0 ? 0.0 : (m > 255.0 ? 255.0 : m);
+    return (int)m;
+}
+// the colour pixel with its cv2 HSV saturation scaled by clip(sat, 0, 10): numpy float64 -> uint8 assignment (wraps above 255)
+__device__ __forceinline__ void restore_desaturate(int& cr, int& cg, int& cb, double sat, bool scale) {
+    int ch, cs, cv;
+    cv_rgb2hsv(cr, cg, cb, ch, cs, cv);
+    if (scale) {
+        const double sc = sat < 0.0 ? 0.0 : (sat > 10.0 ? 10.0 : sat);
+        cs = (int)(uint8_t)(long long)((double)cs * sc);
+    }
+    cv_hsv2rgb(ch, cs, cv, cr, cg, cb);
+}
+// restore_color_gradient: w_np_image_mask_merge(gray, colour, mask, normalize=True), then np_weighted_merge towards the colour pixel (weight > 0) or the
+// gray one (weight < 0); sat == 1.0 leaves the saturation alone (the HSV round trip still runs); return_mask: the mask on the three channels
+__device__ __forceinline__ void restore_gradient_pixel(int cr, int cg, int cb, int gr, int gg, int gb, double sat, int tht, double alpha, double weight,
+                                                       int algo, int return_mask, int o[3]) {
+    int h, s, v;
+    cv_rgb2hsv(gr, gg, gb, h, s, v);
+    const int mask = restore_gradient_mask(s, tht, alpha, algo);
+    if (return_mask) { o[0] = o[1] = o[2] = mask; return; }
+    restore_desaturate(cr, cg, cb, sat, sat != 1.0);
+    const double mw = (double)mask / 255.0, mb = 1.0 - mw;
+    const int src_g[3] = {gr, gg, gb}, src_c[3] = {cr, cg, cb};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double m = (double)src_g[k] * mb + (double)src_c[k] * mw;
+        int r = (int)(m < 0.0 ? 0.0 : (m > 255.0 ? 255.0 : m));
+        if (weight > 0.0) r = wmerge1(r, src_c[k], weight);
+        if (weight < 0.0) r = wmerge1(r, src_g[k], -weight);
+        o[k] = r;
+    }
+}
+// restore_color with tht_scen = 1.0 and hue_adjust 'none' (restcolor.py:38-83; its early return needs tht_scen < 1): mask = 255 where s < tht, else 0;
+// np_image_mask_merge picks the desaturated colour pixel under a white mask (products by exactly 0.0 and 1.0); the saturation product runs for every sat;
+// the weighted merge goes the OTHER way round: weight > 0 towards the gray pixel, weight < 0 towards the desaturated colour pixel
+__device__ __forceinline__ void restore_binary_pixel(int cr, int cg, int cb, int gr, int gg, int gb, double sat, int tht, double weight, int return_mask,
+                                                     int o[3]) {
+    int h, s, v;
+    cv_rgb2hsv(gr, gg, gb, h, s, v);
+    const bool white = s < tht;
+    if (return_mask) { o[0] = o[1] = o[2] = white ? 255 : 0; return; }
+    restore_desaturate(cr, cg, cb, sat, true);
+    const int src_g[3] = {gr, gg, gb}, src_c[3] = {cr, cg, cb};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        int r = white ? src_c[k] : src_g[k];
+        if (weight > 0.0) r = wmerge1(r, src_g[k], weight);
+        if (weight < 0.0) r = wmerge1(r, src_c[k], -weight);
+        o[k] = r;
+    }
 }

@@ -403,6 +403,36 @@ int havc_restore_color_gradient(havc_ctx* c, const uint8_t* img_color, const uin
         return launch_restore_color_gradient(da, db, dout, (int64_t)width * height, sat, tht, alpha, weight, algo, return_mask, c->stream); });
 }
 
+// ---- HAVC_recover_clip_color: ChromaRetentionMerge's selectors on a clip (recover.hip) ----
+static_assert(sizeof(havc_recover_params) == 56, "havc_recover_params layout");
+
+int havc_recover_color_clip(havc_ctx* c, const uint8_t* gray, const uint8_t* color, uint8_t* out, const havc_recover_params* p) {
+    if (!c || !gray || !color || !out || !p) return fail(c, HAVC_E_INVALID, "recover_color_clip: bad args");
+    if (p->n_frames < 1 || p->width <= 0 || p->height <= 0 || (int64_t)p->width * p->height > ((int64_t)1 << 31))
+        return fail(c, HAVC_E_INVALID, "recover_color_clip: bad clip size (at most 2^31 pixels per frame)");
+    if (p->algo < 0 || p->algo > 2) return fail(c, HAVC_E_INVALID, "recover_color_clip: algo must be 0..2");
+    if (p->first_frame < 0) return fail(c, HAVC_E_INVALID, "recover_color_clip: first_frame must be >= 0");
+    const size_t cb = (size_t)p->n_frames * p->height * p->width * 3;
+    auto overlaps = [&](const uint8_t* q) { return (uintptr_t)out < (uintptr_t)q + cb && (uintptr_t)q < (uintptr_t)out + cb; };
+    if (overlaps(gray) || overlaps(color)) return fail(c, HAVC_E_INVALID, "recover_color_clip: out must not alias an input");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    RecoverArgs a{};
+    a.n = p->n_frames; a.h = p->height; a.w = p->width; a.first_frame = p->first_frame;
+    a.sat = p->sat; a.weight = p->weight; a.alpha = p->alpha; a.tht = p->tht; a.algo = p->algo;
+    a.binary_mask = p->binary_mask != 0; a.return_mask = p->return_mask != 0;
+    int rc;
+    const uint8_t *d_gray, *d_color;
+    uint8_t* d_out;
+    bool host;
+    if ((rc = stage_in(c, SCR_IN, gray, cb, &d_gray)) || (rc = stage_in(c, SCR_IN2, color, cb, &d_color)) ||
+        (rc = stage_out_ptr(c, SCR_OUT, out, cb, &d_out, &host)) || (rc = ensure_scratch(c, SCR_SMALL, (size_t)a.n * sizeof(unsigned long long)))) return rc;
+    const int e = launch_recover_color(d_gray, d_color, d_out, (unsigned long long*)c->scratch[SCR_SMALL], a, c->stream);
+    c->stats.launches += 2;
+    if (e) return hip_fail(c, (hipError_t)e, "recover_color_clip");
+    return stage_out(c, out, d_out, cb, host);
+}
+
 int havc_color_temporal_stabilizer(havc_ctx* c, const uint8_t* const* frames, const double* weights, int n, uint8_t* out, int width, int height) {
     if (!c || !frames || !weights || !out || n < 1 || n > 9 || width <= 0 || height <= 0) return fail(c, HAVC_E_INVALID, "color_temporal_stabilizer: bad args (1..9 frames)");
     std::lock_guard<std::mutex> lk(c->mu);

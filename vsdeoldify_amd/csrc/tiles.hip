@@ -17,19 +17,7 @@
 #include "kernels.h"
 #include "pixel_ops.h"
 
-__device__ __forceinline__ void load12(const uint8_t* p, int v[12]) {
-    uint32_t w[3];
-    __builtin_memcpy(w, p, 12);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) v[i] = (int)((w[i >> 2] >> ((i & 3) * 8)) & 255u);
-}
-__device__ __forceinline__ void store12(uint8_t* p, const int v[12]) {
-    uint32_t w[3] = {0u, 0u, 0u};
-#pragma unroll
-    for (int i = 0; i < 12; ++i) w[i >> 2] |= (uint32_t)v[i] << ((i & 3) * 8);
-    __builtin_memcpy(p, w, 12);
-}
-
+// load12 / store12: pixel_ops.h
 __device__ __forceinline__ uint8_t* tile_ptr(const TileArgs& a, int t) { return t == 0 ? a.tile[0] : (t == 1 ? a.tile[1] : (t == 2 ? a.tile[2] : a.tile[3])); }
 
 // ---- slice -------------------------------------------------------------------------------------------------------------------------------------

@@ -68,68 +68,14 @@ int launch_luma_lut(const uint8_t* img, const uint8_t* d_lut, uint8_t* out, int6
     return (int)hipGetLastError();
 }
 
-// ---- restore_color_gradient (restcolor.py:98-217) ----
+// ---- restore_color_gradient (restcolor.py:98-217): one frame; the pixel is pixel_ops.h's restore_gradient_pixel, shared with recover.hip ----
 __global__ void restore_color_gradient_kernel(const uint8_t* __restrict__ color, const uint8_t* __restrict__ gray, uint8_t* __restrict__ out,
                                               int64_t npix, double sat, int tht, double alpha, double weight, int algo, int return_mask) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
-        const int gr = gray[i * 3], gg = gray[i * 3 + 1], gb = gray[i * 3 + 2];
-        int h, s, v;
-        cv_rgb2hsv(gr, gg, gb, h, s, v);
-        // gradient mask from the saturation of the "gray" image: white (255) where it is gray
-        int mask;
-        if (algo == 0) {
-            const double sd = (double)s;
-            const double grad = s < tht ? 2.0 * sd / alpha - (double)tht : 2.0 * (sd - (double)tht) * alpha;
-            double m = 255.0 - (double)tht - grad;
-            m = m < 0.0 ? 0.0 : (m > 255.0 ? 255.0 : m);
-            mask = (int)m;
-        } else {
-            const int t = tht < 0 ? 0 : (tht > 255 ? 255 : tht);
-            if (t == 0) mask = 0;
-            else {
-                const float sf = (float)s;
-                double mn;
-                if (algo == 1) {
-                    const float max_s = (float)min(2 * t, 200);
-                    const float sc = fminf(fmaxf(sf, 0.f), max_s);
-                    mn = (double)powf(1.0f - sc / max_s, (float)alpha);
-                } else {
-                    const float s_rel = fminf(fmaxf(sf / (float)t, 0.f), 2.f);
-                    mn = exp((double)((float)(-alpha) * s_rel) * 0.6931471805599453);
-                    if (sf >= (float)(2 * t)) mn = 0.0;
-                }
-                double m = mn * 255.0;
-                m = m < 0.0 ? 0.0 : (m > 255.0 ? 255.0 : m);
-                mask = (int)m;
-            }
-        }
-        if (return_mask) { out[i * 3] = out[i * 3 + 1] = out[i * 3 + 2] = (uint8_t)mask; continue; }
-        int cr = color[i * 3], cg = color[i * 3 + 1], cb = color[i * 3 + 2];
-        {
-            int ch, cs, cv;
-            cv_rgb2hsv(cr, cg, cb, ch, cs, cv);
-            if (sat != 1.0) {
-                const double sc = sat < 0.0 ? 0.0 : (sat > 10.0 ? 10.0 : sat);
-                cs = (int)(uint8_t)(long long)((double)cs * sc);          // numpy float64 -> uint8 assignment (wraps above 255)
-            }
-            cv_hsv2rgb(ch, cs, cv, cr, cg, cb);
-        }
-        const double mw = (double)mask / 255.0, mb = 1.0 - mw;
-        const int src_g[3] = {gr, gg, gb}, src_c[3] = {cr, cg, cb};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            double m = (double)src_g[k] * mb + (double)src_c[k] * mw;
-            int o = (int)(m < 0.0 ? 0.0 : (m > 255.0 ? 255.0 : m));
-            if (weight > 0.0) {
-                m = (double)o * (1.0 - weight) + (double)src_c[k] * weight;
-                o = (int)(m < 0.0 ? 0.0 : (m > 255.0 ? 255.0 : m));
-            }
-            if (weight < 0.0) {
-                m = (double)o * (1.0 - (-weight)) + (double)src_g[k] * (-weight);
-                o = (int)(m < 0.0 ? 0.0 : (m > 255.0 ? 255.0 : m));
-            }
-            out[i * 3 + k] = (uint8_t)o;
-        }
+        int o[3];
+        restore_gradient_pixel(color[i * 3], color[i * 3 + 1], color[i * 3 + 2], gray[i * 3], gray[i * 3 + 1], gray[i * 3 + 2], sat, tht, alpha, weight, algo,
+                               return_mask, o);
+        out[i * 3] = (uint8_t)o[0]; out[i * 3 + 1] = (uint8_t)o[1]; out[i * 3 + 2] = (uint8_t)o[2];
     }
 }
 int launch_restore_color_gradient(const uint8_t* color, const uint8_t* gray, uint8_t* out, int64_t npix, double sat, int tht, double alpha,

@@ -9,6 +9,7 @@
     HAVC_DeepRemaster vsdeoldify/__init__.py:2689-2735    (mode 0: reference stills from a directory; remaster_render.RemasterRender; fast mode only)
     HAVC_extract_reference_frames vsdeoldify/__init__.py:3272-3351   (sc_algo 0: SceneDetect + the SSIM / histogram post-filter, then ref_nnnnnn.jpg|png on disk)
     HAVC_export_reference_frames  vsdeoldify/__init__.py:3364-3385   HAVC_export_list_frames vsdeoldify/__init__.py:3387-3416   (the writers alone)
+    HAVC_recover_clip_color vsdeoldify/__init__.py:2956-2992   (ChromaRetentionMerge on a clip: gradient and binary mask, chroma_resize through the library's Spline64)
 
 Same names, argument lists, defaults, parameter normalisation, frame-size rule, model routing, combine dispatch
 (vsslib/mcomb.py:125-192) and error texts; a "clip" is a uint8 array [n, h, w, 3] (or one frame [h, w, 3], or a
@@ -369,8 +370,8 @@ def combine_models(a, b, method, w, cmc_p=DEF_CMC_p, lmm_p=DEF_LMM_p, alm_p=DEF_
     if method == 5:
         return _per_frame(lambda x, y: mcomb.adaptive_luma_merge(x, y, alm_p[0], alm_p[1], w, alm_p[2], di), a, b)
     if method == 6:
-        if crt_p[3]:
-            raise NotImplementedError("ChromaRetentionMerge(chroma_resize=True) is a VapourSynth-level resize round trip")
+        if crt_p[3]:                                                         # chroma_resize: the whole of ChromaRetentionMerge on the clip (Spline64 stand-in)
+            return mcomb.chroma_retention_merge_clip(a, b, crt_p[0], crt_p[1], w, crt_p[2], crt_p[4], True, False, False, crt_p[5], 0, di)
         restored = _per_frame(lambda x, y: mcomb.chroma_retention_frame(x, y, crt_p[0], crt_p[1], crt_p[4], crt_p[2], False, crt_p[5], di), a, b)
         return unrows(mcomb.simple_merge(rows(a), rows(restored), w, di))   # vs_simple_merge = std.Merge in the reference (VapourSynth core)
     if method == 7:
@@ -476,6 +477,32 @@ def HAVC_merge(clipa=None, clipb=None, clip_luma=None, weight=0.5, method=2, cmc
     if clip_luma is not None:                                                                     # __init__.py:2673-2676
         merged = _clip_chroma_resize(clip_luma, merged, device_index)
     return done(merged)
+
+
+# ---- HAVC_recover_clip_color (vsdeoldify/__init__.py:2956-2992) ---------------------------------------------------------------------------------
+def HAVC_recover_clip_color(clip=None, clip_color=None, sat=0.8, tht=30, strength=1.0, alpha=2.0, mask_weight=1.0, chroma_resize=True, return_mask=False,
+                            binary_mask=False, algo=0, *, device_index=0):
+    """vsdeoldify/__init__.py:2956-2992: restore the colours of the gray pixels of `clip` with those of `clip_color` ("useful to repair the clips colored with
+    DeepRemaster") = ChromaRetentionMerge(clip, clip_color, sat, tht, clipb_weight=strength, alpha, mask_weight, scenechange=False, chroma_resize, return_mask,
+    binary_mask, algo) -> mcomb.chroma_retention_merge_clip: one havc_recover_color_clip call (two launches over the whole clip) between the Spline64 round
+    trip of chroma_resize and the closing merge.  ndarray in -> ndarray out; DeviceImage in -> DeviceImage out (nothing leaves HBM, the call only enqueues);
+    one of each: the ndarray is uploaded.  A frame [h, w, 3] in -> a frame out.  Frame 0 of the operand is clip frame 0 (the binary selector's `n < 15`)."""
+    for c in (clip, clip_color):                                                                  # __init__.py:2983-2984 (the text names HAVC_merge there)
+        if c is None or not (is_device(c) or isinstance(c, np.ndarray)):
+            raise HAVCError("HAVC_merge: this is not a clip: clip_color")
+    for c in (clip, clip_color):
+        if c.ndim not in (3, 4) or c.shape[-1] != 3 or (not is_device(c) and c.dtype != np.uint8):
+            raise HAVCError("HAVC: only RGB24 clips (uint8 [n, h, w, 3]) are supported")
+    if tuple(clip.shape) != tuple(clip_color.shape):
+        raise HAVCError(f"HAVC_recover_clip_color: clip {tuple(clip.shape)} and clip_color {tuple(clip_color.shape)} differ in size")
+    if algo not in (0, 1, 2):
+        raise HAVCError(f"HAVC_recover_clip_color: algo = {algo}: only 0, 1, 2 are supported")
+    a, single = _as_clip(clip)
+    b, _ = _as_clip(clip_color)
+    out = mcomb.chroma_retention_merge_clip(a, b, sat, tht, strength, alpha, mask_weight, chroma_resize, return_mask, binary_mask, algo, 0, device_index)
+    if is_device(out):
+        return out.reshaped(out.shape[1:]) if single else out
+    return out[0] if single else out
 
 
 # ---- HAVC_stabilizer (vsdeoldify/__init__.py:2748-2873) ----------------------------------------------------------------------------------------
