@@ -372,8 +372,12 @@ int havc_deoldify_frame_planar(havc_ctx* ctx, havc_net* video, havc_net* second,
  * row stride <-> interleaved RGB, w x h */
 int havc_planar_to_rgb8(havc_ctx* ctx, const uint8_t* const planes[3], int stride, uint8_t* rgb, int width, int height);
 int havc_rgb8_to_planar(havc_ctx* ctx, const uint8_t* rgb, uint8_t* const planes[3], int stride, int width, int height);
-/* Pillow Image.resize (BILINEAR = 2, BICUBIC = 3), 8 bits per channel, bit-exact (libImaging/Resample.c) */
+/* Pillow Image.resize (LANCZOS = 1, BILINEAR = 2, BICUBIC = 3), 8 bits per channel, bit-exact (libImaging/Resample.c): 22-bit fixed-point
+ * coefficients, horizontal pass before the vertical one.  src and dst may be host or device memory (device operands are used in place and the call
+ * only enqueues).  The two passes walk each output's own bounds, so any tap count runs (LANCZOS: 3 x the down-sampling ratio on either side). */
 int havc_pil_resize(havc_ctx* ctx, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, int resample);
+/* n_frames tightly packed frames per operand in one call: the coefficient tables are built and uploaded once for all of them */
+int havc_pil_resize_n(havc_ctx* ctx, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, int resample, int n_frames);
 
 /* ---- per-pixel filters on host buffers (vsslib/imfilters.py); u8 interleaved RGB, w*h pixels ---- */
 /* Image.blend(a, b, w): trunc(a + w*(b-a)) in fp32 — image_weighted_merge, imfilters.py:113-124 */
@@ -610,11 +614,20 @@ int havc_spline64_resize_n(havc_ctx* ctx, const uint8_t* src, int sw, int sh, ui
  * HAVC_E_INVALID.  Host arithmetic only: no context, no GPU call.  The launcher takes its decision from the same function, so tests can pin which kernel a
  * shape exercises. */
 int havc_resize_plan(int sw, int dw, int n_rows, int* h_taps, int* h_variant);
+/* The same separable resize with the kernel chosen by `filter`: HAVC_RESIZE_SPLINE64 (what havc_spline64_resize_n runs: the same tables, launches and
+ * bytes) or HAVC_RESIZE_SPLINE36, the stand-in for zimg's `resize.Spline36` (HAVC_restore_video brings clip_ref to the clip's size with it,
+ * `__init__.py:2057-2058`): support 3, widened by the down-sampling ratio like Spline64's 4; the same passes, variants and fused luma_from. */
+#define HAVC_RESIZE_SPLINE64 0
+#define HAVC_RESIZE_SPLINE36 1
+int havc_resize_n(havc_ctx* ctx, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, const uint8_t* luma_from, int n_frames, int filter);
+/* havc_resize_plan for a filter of havc_resize_n */
+int havc_resize_plan_filter(int sw, int dw, int n_rows, int filter, int* h_taps, int* h_variant);
 int havc_dev_alloc(havc_ctx* ctx, size_t nbytes, void** out);
 int havc_dev_free(havc_ctx* ctx, void* p);
 int havc_dev_upload(havc_ctx* ctx, void* d_dst, const void* h_src, size_t nbytes);
 int havc_dev_download(havc_ctx* ctx, void* h_dst, const void* d_src, size_t nbytes);
 int havc_dev_copy(havc_ctx* ctx, void* d_dst, const void* d_src, size_t nbytes);      /* device -> device, enqueued on the ctx stream */
+int havc_dev_memset(havc_ctx* ctx, void* d_dst, int value, size_t nbytes);            /* byte fill of device memory, enqueued on the ctx stream */
 
 /* ---- ColorMNet exemplar path: the memory kernels (fp32, the reference's tensor layouts, host or device pointers) ----
  * havc_memory_read_topk replaces get_similarity + do_softmax(top_k) + readout (colormnet/model/memory_util.py:7-80) as

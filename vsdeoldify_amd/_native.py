@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HAVC_MI355_LIB") or os.path.join(_HERE, "lib", "libhavc_mi355.so")   # override: A/B builds in tools/
 
 HAVC_OK, HAVC_E_INVALID, HAVC_E_OOM, HAVC_E_HIP, HAVC_E_NODEVICE, HAVC_E_RANGE = 0, -1, -2, -3, -4, -5
+RESIZE_SPLINE64, RESIZE_SPLINE36 = 0, 1                   # havc_resize_n's filter
 
 # op types / flags (mirror include/havc_mi355.h)
 OP_CONV, OP_MAXPOOL, OP_BLUR_RESIZE, OP_AFFINE, OP_ATTENTION, OP_PREP_RGB8, OP_COPY_CH = 1, 2, 3, 4, 5, 6, 7
@@ -146,6 +147,8 @@ SYMBOLS = [
     ("havc_zhang_frames", _I, [_P, _P, _P, _P, _I, _I, _I]),
     ("havc_ddcolor_frames", _I, [_P, _P, _P, _P, _I, _I, _I]),
     ("havc_pil_resize", _I, [_P, _P, _I, _I, _P, _I, _I, _I]),
+    ("havc_pil_resize_n", _I, [_P, _P, _I, _I, _P, _I, _I, _I, _I]),
+    ("havc_dev_memset", _I, [_P, _P, _I, _SZ]),
     ("havc_blend", _I, [_P, _P, _P, _F, _P, _I, _I]),
     ("havc_chroma_post_process", _I, [_P, _P, _P, _P, _I, _I]),
     ("havc_chroma_stabilizer", _I, [_P, _P, _P, _D, _D, _P, _I, _I]),
@@ -174,6 +177,8 @@ SYMBOLS = [
     ("havc_spline64_resize", _I, [_P, _P, _I, _I, _P, _I, _I, _P]),
     ("havc_spline64_resize_n", _I, [_P, _P, _I, _I, _P, _I, _I, _P, _I]),
     ("havc_resize_plan", _I, [_I, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
+    ("havc_resize_n", _I, [_P, _P, _I, _I, _P, _I, _I, _P, _I, _I]),
+    ("havc_resize_plan_filter", _I, [_I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
     ("havc_colorize_clip_host", _I, [_P, _P, _P, _F, _P, _P, _I, _I, _I]),
     ("havc_host_alloc", _I, [_P, _SZ, C.POINTER(_P)]),
     ("havc_host_free", _I, [_P, _P]),

@@ -105,7 +105,7 @@ class ModelColorization:
 
 
 def pil_resize_np(ctx, img, size, resample):
-    """Pillow Image.resize((w, h), resample) on the GPU, bit-exact (BILINEAR = 2, BICUBIC = 3)."""
+    """Pillow Image.resize((w, h), resample) on the GPU, bit-exact (LANCZOS = 1, BILINEAR = 2, BICUBIC = 3)."""
     img = np.ascontiguousarray(img, dtype=np.uint8)
     out = np.empty((size[1], size[0], 3), np.uint8)
     nat.check(ctx.lib.havc_pil_resize(ctx.h, nat.as_ptr(img), img.shape[1], img.shape[0], nat.as_ptr(out), size[0], size[1], resample), ctx.h)

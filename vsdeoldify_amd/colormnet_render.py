@@ -300,8 +300,6 @@ class DeepExColorMNet:
             raise ValueError("HAVC_deepex: unknown render_speed ->" + render_speed)
         scale = 2 if enable_resize else 1
         self.th, self.tw = (v * scale for v in DEEPEX_SIZES[render_speed.lower()])
-        if max_memory_frames > 0:
-            render_vivid = False                                          # __init__.py:1692-1693
         self.propagate = frame_propagate
         self.render = ColorMNetRender(image_size=-1, vid_length=vid_length, enable_resize=enable_resize, encode_mode=1, max_memory_frames=max_memory_frames,
                                       reset_on_ref_update=render_vivid, project_dir=project_dir, state_dict=state_dict, device_index=device_index,

@@ -349,6 +349,14 @@ int havc_dev_copy(havc_ctx* c, void* d_dst, const void* d_src, size_t nbytes) {
     return HAVC_OK;
 }
 
+int havc_dev_memset(havc_ctx* c, void* d_dst, int value, size_t nbytes) {
+    if (!c || !d_dst) return HAVC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    HIP_TRY(c, hipMemsetAsync(d_dst, value, nbytes, c->stream));                               // ordered on the ctx stream, does not block
+    return HAVC_OK;
+}
+
 int havc_tag_timing_enable(havc_ctx* c, int tag, int enable) {
     if (!c) return HAVC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mu);

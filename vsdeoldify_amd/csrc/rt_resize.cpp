@@ -1,4 +1,4 @@
-// libhavc_mi355.so runtime, resampling: the Spline64 and Pillow coefficient tables and their resize entry points.
+// libhavc_mi355.so runtime, resampling: the Spline64 / Spline36 and Pillow coefficient tables and their resize entry points.
 #include "runtime_internal.h"
 
 namespace {
@@ -13,18 +13,30 @@ double spline64(double x) {
     return 0.0;
 }
 
+// ---- Spline36 (Avisynth/zimg Spline36 kernel, support 3): the same polyphase tables with another kernel ----
+double spline36(double x) {
+    x = std::fabs(x);
+    if (x < 1.0) return ((13.0 / 11.0 * x - 453.0 / 209.0) * x - 3.0 / 209.0) * x + 1.0;
+    if (x < 2.0) { x -= 1.0; return ((-6.0 / 11.0 * x + 270.0 / 209.0) * x - 156.0 / 209.0) * x; }
+    if (x < 3.0) { x -= 2.0; return ((1.0 / 11.0 * x - 45.0 / 209.0) * x + 26.0 / 209.0) * x; }
+    return 0.0;
+}
+
+bool resize_filter_ok(int filter) { return filter == HAVC_RESIZE_SPLINE64 || filter == HAVC_RESIZE_SPLINE36; }
+double resize_support(int filter) { return filter == HAVC_RESIZE_SPLINE36 ? 3.0 : 4.0; }
+
 // kernel stretch for anti-aliasing when downscaling, and the taps per output of a src -> dst pass (the table below and havc_resize_plan)
 double resize_fscale(int src, int dst) { const double scale = (double)dst / (double)src; return scale < 1.0 ? scale : 1.0; }
-int resize_taps(int src, int dst) { return (int)std::ceil(2.0 * (4.0 / resize_fscale(src, dst))) + 1; }
+int resize_taps(int src, int dst, int filter) { return (int)std::ceil(2.0 * (resize_support(filter) / resize_fscale(src, dst))) + 1; }
 
-int get_resize_table(havc_ctx* c, int src, int dst, ResizeTable** out) {
-    auto key = std::make_pair(src, dst);
+int get_resize_table(havc_ctx* c, int src, int dst, int filter, ResizeTable** out) {
+    auto key = std::make_tuple(src, dst, filter);
     auto it = c->resize_tables.find(key);
     if (it != c->resize_tables.end()) { *out = &it->second; return HAVC_OK; }
     const double scale = (double)dst / (double)src;
     const double fscale = resize_fscale(src, dst);
-    const double support = 4.0 / fscale;
-    const int taps = resize_taps(src, dst);
+    const double support = resize_support(filter) / fscale;
+    const int taps = resize_taps(src, dst, filter);
     std::vector<int> start(dst);
     std::vector<float> w((size_t)dst * taps);
     for (int i = 0; i < dst; ++i) {
@@ -32,7 +44,7 @@ int get_resize_table(havc_ctx* c, int src, int dst, ResizeTable** out) {
         const int s0 = (int)std::floor(center - support) + 1;
         double sum = 0;
         std::vector<double> tmp(taps);
-        for (int t = 0; t < taps; ++t) { tmp[t] = spline64((s0 + t - center) * fscale); sum += tmp[t]; }
+        for (int t = 0; t < taps; ++t) { const double xk = (s0 + t - center) * fscale; tmp[t] = filter == HAVC_RESIZE_SPLINE36 ? spline36(xk) : spline64(xk); sum += tmp[t]; }
         for (int t = 0; t < taps; ++t) w[(size_t)i * taps + t] = (float)(tmp[t] / sum);
         start[i] = s0;
     }
@@ -51,11 +63,11 @@ int get_resize_table(havc_ctx* c, int src, int dst, ResizeTable** out) {
 }  // namespace
 
 int resize_rgb8(havc_ctx* c, const uint8_t* d_src, int sw, int sh, uint8_t* d_dst, int dw, int dh, int n,
-                const uint8_t* d_orig) {
+                const uint8_t* d_orig, int filter) {
     ResizeTable *th, *tv;
-    int rc = get_resize_table(c, sw, dw, &th);
+    int rc = get_resize_table(c, sw, dw, filter, &th);
     if (rc) return rc;
-    rc = get_resize_table(c, sh, dh, &tv);
+    rc = get_resize_table(c, sh, dh, filter, &tv);
     if (rc) return rc;
     rc = ensure_scratch(c, SCR_RESIZE_ROWS, (size_t)n * sh * dw * 3 * sizeof(float));
     if (rc) return rc;
@@ -72,6 +84,10 @@ namespace {
 struct PilTable { int ksize = 0; int* d_bounds = nullptr; int* d_kk = nullptr; };
 
 double pil_filter(int resample, double x) {
+    if (resample == 1) {                                                      // LANCZOS: lanczos_filter, a = 3, on [-3, 3) of the signed x
+        auto sinc = [](double v) { if (v == 0.0) return 1.0; v *= M_PI; return std::sin(v) / v; };
+        return (-3.0 <= x && x < 3.0) ? sinc(x) * sinc(x / 3.0) : 0.0;
+    }
     if (x < 0.0) x = -x;
     if (resample == 2) return x < 1.0 ? 1.0 - x : 0.0;                       // BILINEAR
     const double a = -0.5;                                                    // BICUBIC
@@ -81,7 +97,7 @@ double pil_filter(int resample, double x) {
 }
 
 int build_pil_table(havc_ctx* c, int in_size, int out_size, int resample, PilTable* tb) {
-    const double fsupport = resample == 2 ? 1.0 : 2.0;
+    const double fsupport = resample == 2 ? 1.0 : (resample == 1 ? 3.0 : 2.0);
     const double scale = (double)in_size / (double)out_size;
     double filterscale = scale < 1.0 ? 1.0 : scale;
     const double support = fsupport * filterscale;
@@ -136,23 +152,31 @@ int pil_resize_dev(havc_ctx* c, const uint8_t* d_src, int sw, int sh, uint8_t* d
 extern "C" {
 
 int havc_pil_resize(havc_ctx* c, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, int resample) {
-    if (!c || !src || !dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || (resample != 2 && resample != 3))
-        return fail(c, HAVC_E_INVALID, "pil_resize: bad args (resample must be 2 = BILINEAR or 3 = BICUBIC)");
+    return havc_pil_resize_n(c, src, sw, sh, dst, dw, dh, resample, 1);
+}
+
+int havc_pil_resize_n(havc_ctx* c, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, int resample, int n_frames) {
+    if (!c || !src || !dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || n_frames < 1 || (resample != 1 && resample != 2 && resample != 3))
+        return fail(c, HAVC_E_INVALID, "pil_resize: bad args (resample must be 1 = LANCZOS, 2 = BILINEAR or 3 = BICUBIC)");
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(c, hipSetDevice(c->dev));
     int rc;
-    const size_t sb = (size_t)sw * sh * 3, tb = (size_t)sh * dw * 3, db = (size_t)dw * dh * 3;
+    const size_t sb = (size_t)sw * sh * 3 * n_frames, tb = (size_t)sh * dw * 3 * n_frames, db = (size_t)dw * dh * 3 * n_frames;
     const uint8_t* d_src;
     uint8_t* d_dst;
     bool host;
     if ((rc = stage_in(c, SCR_IN, src, sb, &d_src)) || (rc = ensure_scratch(c, SCR_PIL_ROWS, tb)) || (rc = stage_out_ptr(c, SCR_OUT, dst, db, &d_dst, &host))) return rc;
-    if ((rc = pil_resize_dev(c, d_src, sw, sh, (uint8_t*)c->scratch[SCR_PIL_ROWS], d_dst, dw, dh, 1, resample))) return rc;
+    if ((rc = pil_resize_dev(c, d_src, sw, sh, (uint8_t*)c->scratch[SCR_PIL_ROWS], d_dst, dw, dh, n_frames, resample))) return rc;
     return stage_out(c, dst, d_dst, db, host);
 }
 
 int havc_resize_plan(int sw, int dw, int n_rows, int* h_taps, int* h_variant) {
-    if (sw <= 0 || dw <= 0 || n_rows <= 0) return HAVC_E_INVALID;
-    const int taps = resize_taps(sw, dw);
+    return havc_resize_plan_filter(sw, dw, n_rows, HAVC_RESIZE_SPLINE64, h_taps, h_variant);
+}
+
+int havc_resize_plan_filter(int sw, int dw, int n_rows, int filter, int* h_taps, int* h_variant) {
+    if (sw <= 0 || dw <= 0 || n_rows <= 0 || !resize_filter_ok(filter)) return HAVC_E_INVALID;
+    const int taps = resize_taps(sw, dw, filter);
     int span_lds = 0;
     const int variant = resize_h_variant(sw, dw, taps, n_rows, &span_lds);
     if (h_taps) *h_taps = taps;
@@ -165,7 +189,12 @@ int havc_spline64_resize(havc_ctx* c, const uint8_t* src, int sw, int sh, uint8_
 }
 
 int havc_spline64_resize_n(havc_ctx* c, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, const uint8_t* luma_from, int n_frames) {
-    if (!c || !src || !dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || n_frames < 1) return fail(c, HAVC_E_INVALID, "spline64_resize: bad args");
+    return havc_resize_n(c, src, sw, sh, dst, dw, dh, luma_from, n_frames, HAVC_RESIZE_SPLINE64);
+}
+
+int havc_resize_n(havc_ctx* c, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, const uint8_t* luma_from, int n_frames, int filter) {
+    if (!c || !src || !dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || n_frames < 1) return fail(c, HAVC_E_INVALID, "resize_n: bad args");
+    if (!resize_filter_ok(filter)) return fail(c, HAVC_E_INVALID, "resize: filter must be 0 = Spline64 or 1 = Spline36");
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(c, hipSetDevice(c->dev));
     const size_t sb = (size_t)sw * sh * 3 * n_frames, db = (size_t)dw * dh * 3 * n_frames;
@@ -177,7 +206,7 @@ int havc_spline64_resize_n(havc_ctx* c, const uint8_t* src, int sw, int sh, uint
         (luma_from && (rc = stage_in(c, SCR_IN3, luma_from, db, &d_luma)))) return rc;
     if (sw == dw && sh == dh && !luma_from) {
         HIP_TRY(c, hipMemcpyAsync(d_dst, d_src, sb, hipMemcpyDeviceToDevice, c->stream));
-    } else if ((rc = resize_rgb8(c, d_src, sw, sh, d_dst, dw, dh, n_frames, d_luma)))
+    } else if ((rc = resize_rgb8(c, d_src, sw, sh, d_dst, dw, dh, n_frames, d_luma, filter)))
         return rc;
     return stage_out(c, dst, d_dst, db, host);
 }

@@ -13,6 +13,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <vector>
 
 // Set-up is serialised process-wide (rt_context.cpp says what counts as set-up and why).
@@ -124,7 +125,7 @@ struct havc_ctx {
     size_t scratch_sz[SCR_COUNT] = {0};
     hipStream_t stream_h2d = nullptr, stream_d2h = nullptr;      // copy streams of havc_colorize_clip_host (created on first use)
     hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_down[2] = {nullptr, nullptr};
-    std::map<std::pair<int, int>, ResizeTable> resize_tables;
+    std::map<std::tuple<int, int, int>, ResizeTable> resize_tables;       // (src, dst, filter)
     // per-tag timing
     int timed_tag = -1;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> tag_events;
@@ -188,7 +189,7 @@ int ensure_scratch(havc_ctx* c, int slot, size_t nbytes);                       
 // ---- functions that cross units ----
 int run_ops_locked(havc_net* n, int first, int count, int batch);                           // rt_net.cpp
 int net_run_rgb8_locked(havc_net* n, const uint8_t* d_in, uint8_t* d_out, int batch, hipStream_t on = nullptr);
-int resize_rgb8(havc_ctx* c, const uint8_t* d_src, int sw, int sh, uint8_t* d_dst, int dw, int dh, int n, const uint8_t* d_orig);   // rt_resize.cpp
+int resize_rgb8(havc_ctx* c, const uint8_t* d_src, int sw, int sh, uint8_t* d_dst, int dw, int dh, int n, const uint8_t* d_orig, int filter = 0);   // rt_resize.cpp
 int pil_resize_dev(havc_ctx* c, const uint8_t* d_src, int sw, int sh, uint8_t* d_tmp, uint8_t* d_dst, int dw, int dh, int n, int resample);
 
 inline void* bufptr(havc_net* n, int id) {

@@ -10,6 +10,7 @@
     HAVC_extract_reference_frames vsdeoldify/__init__.py:3272-3351   (sc_algo 0: SceneDetect + the SSIM / histogram post-filter, then ref_nnnnnn.jpg|png on disk)
     HAVC_export_reference_frames  vsdeoldify/__init__.py:3364-3385   HAVC_export_list_frames vsdeoldify/__init__.py:3387-3416   (the writers alone)
     HAVC_recover_clip_color vsdeoldify/__init__.py:2956-2992   (ChromaRetentionMerge on a clip: gradient and binary mask, chroma_resize through the library's Spline64)
+    HAVC_restore_video vsdeoldify/__init__.py:1959-2127   (colour transfer from a reference video: ex_model 0 = ColorMNet, 2 = DeepRemaster's clip mode; methods 5, 6)
 
 Same names, argument lists, defaults, parameter normalisation, frame-size rule, model routing, combine dispatch
 (vsslib/mcomb.py:125-192) and error texts; a "clip" is a uint8 array [n, h, w, 3] (or one frame [h, w, 3], or a
@@ -25,7 +26,8 @@ pre-tweaks that are VapourSynth filters (`ddtweak`: bright / cont / gamma throug
 Computed here: the hue adjustment vs_sc_ddcolor applies to every DDColor frame (default "300:360|0.8,0.1") and the luma-constrained
 pre-tweak with its luma recovery (HAVCFrameColorizer._read_ddtweak).  What stands in for VapourSynth native code (outside the parity
 contract; none of it can be executed where the fixtures are made, so its integer rounding is unpinned):
-  * zimg's `resize.Spline64` -> the library's own Spline64;
+  * zimg's `resize.Spline64` -> the library's own Spline64; zimg's `resize.Spline36` (HAVC_restore_video: clip_ref to the clip's size) -> the library's own
+    Spline36, the same passes with the other kernel;
   * `std.MaskedMerge` under an `akarin.Expr` position mask (HAVC_clip_reconstruct's row and column blends, vsslib/vstiles4.py:281-349) ->
     out = (a * (255 - m) + b * m + 127) // 255 per channel, rounded to uint8 after each of the two blends; m = 0 gives a and m = 255 gives b exactly;
   * `vsresize.resize_to_chroma` (HAVC_clip_reconstruct(chroma_resize=True), vsslib/vsresize.py:101-127: a zimg YUV420P8 round trip, BT.709) -> the
@@ -314,6 +316,15 @@ class HAVCFrameColorizer:
 def spline64(ctx, img, w, h, luma_from=None):
     """the harness stand-in of `resize.Spline64` (+ vs_recover_clip_luma when luma_from is given) on frames or clips,
     host or device operands"""
+    return _resize(ctx, img, w, h, luma_from, None)
+
+
+def spline36(ctx, img, w, h, luma_from=None):
+    """the harness stand-in of `resize.Spline36`: the same passes with the Spline36 kernel (havc_resize_n)"""
+    return _resize(ctx, img, w, h, luma_from, nat.RESIZE_SPLINE36)
+
+
+def _resize(ctx, img, w, h, luma_from, filter_id):
     dev = is_device(img) or is_device(luma_from)
     if dev:
         img = img if is_device(img) else DeviceImage.from_numpy(ctx, img)
@@ -329,8 +340,8 @@ def spline64(ctx, img, w, h, luma_from=None):
         raise ValueError("luma_from must have the output shape")
     out = DeviceImage(ctx, shape) if dev else np.empty(shape, np.uint8)
     from .device import operand_ptr
-    nat.check(ctx.lib.havc_spline64_resize_n(ctx.h, operand_ptr(img), sw, sh, operand_ptr(out), w, h,
-                                             operand_ptr(luma_from) if luma_from is not None else None, n), ctx.h)
+    args = (ctx.h, operand_ptr(img), sw, sh, operand_ptr(out), w, h, operand_ptr(luma_from) if luma_from is not None else None, n)
+    nat.check(ctx.lib.havc_spline64_resize_n(*args) if filter_id is None else ctx.lib.havc_resize_n(*args, filter_id), ctx.h)
     return out
 
 
@@ -953,9 +964,11 @@ def HAVC_deepex(clip=None, clip_ref=None, method=0, render_speed='medium', rende
     from .colormnet_render import DeepExColorMNet
     from .stabilizer import stabilize_np
     enable_refmerge = ref_merge > 0 and scenes.sc_frequency == 1                                  # __init__.py:1630-1645
+    if max_memory_frames > 0:
+        render_vivid = False                                                                      # __init__.py:1692-1693: HAVC_deepex alone, not HAVC_restore_video
     dx = DeepExColorMNet(vid_length=n, render_speed=render_speed, enable_resize=False, render_vivid=render_vivid, max_memory_frames=max_memory_frames,
                          frame_propagate=False, project_dir=torch_dir, state_dict=harness.get("state_dict"), device_index=harness.get("device_index", 0),
-                         network=harness.get("network"))                                          # (max_memory_frames > 0 switches render_vivid off there)
+                         network=harness.get("network"))
     ctx = dx.ctx
     clip_sc = None
     if enable_refmerge:
@@ -969,6 +982,20 @@ def HAVC_deepex(clip=None, clip_ref=None, method=0, render_speed='medium', rende
         clip_sc = scdetect.scene_detect(ctx, clip, threshold=ref_thresh, frequency=ref_freq, frame_norm=ref_norm, coeffs=coeffs)
     else:
         ref_weight = 1.0
+    tweak = None
+    if dark_args or smooth_args or colormap_adjust:
+        def tweak(sq):
+            return stabilize_np(ctx, sq, dark_args, smooth_args, colormap_adjust, order=("colormap", "dark", "smooth"))            # __init__.py:1679-1689
+    return _colormnet_clip(dx, clip, clip_ref, scenes, clip_sc, ref_weight, single, tweak, harness.get("debug"))
+
+
+def _colormnet_clip(dx, clip, clip_ref, scenes, clip_sc, ref_weight, single, tweak=None, debug=None):
+    """vs_colormnet's frame loop (colormnet/__init__.py) on 4-D operands, shared by HAVC_deepex and HAVC_restore_video: every frame `scenes` flags (and
+    frame 0) hands its clip_ref frame to ColorMNet as the new reference; with 0 < ref_weight < 1 and a clip_sc the flags come from clip_sc instead and
+    every frame that is no scene change is blended with its squashed reference frame.  tweak: applied to the squashed reference frames that `scenes`
+    flags (HAVC_deepex's colormap / dark / smooth)."""
+    ctx = dx.ctx
+    n = clip.shape[0]
     host_in = not is_device(clip)
     dclip = DeviceImage.from_numpy(ctx, clip) if host_in else clip
     dref = clip_ref if is_device(clip_ref) else DeviceImage.from_numpy(ctx, clip_ref)
@@ -980,13 +1007,12 @@ def HAVC_deepex(clip=None, clip_ref=None, method=0, render_speed='medium', rende
         """clip_ref's frame i at the DeepEx size (SmartResizeReference), tweaked where clip_ref's own props make it a scene change (vs_sc_*)"""
         if i not in ref_small:
             sq, _ = dx._squash(dref.frame(i))
-            if (i == 0 or scenes.scene_change_prev[i] == 1) and (dark_args or smooth_args or colormap_adjust):
-                sq = stabilize_np(ctx, sq, dark_args, smooth_args, colormap_adjust, order=("colormap", "dark", "smooth"))      # __init__.py:1679-1689
+            if (i == 0 or scenes.scene_change_prev[i] == 1) and tweak is not None:
+                sq = tweak(sq)
             ref_small[i] = sq
         return ref_small[i]
 
     out = DeviceImage(ctx, dclip.shape)
-    debug = harness.get("debug")
     for i in range(n):
         is_sc = flags.scene_change_prev[i] == 1
         col = dx.colorize_frame(dclip.frame(i), ref_small=small_ref(i) if (i == 0 or is_sc) else None,
@@ -1115,3 +1141,122 @@ def HAVC_DeepRemaster(clip, length=2, render_vivid=False, ref_dir=None, ref_mine
         return out.reshaped(out.shape[1:]) if single else out
     finally:
         engine.close()
+
+
+# ---- HAVC_restore_video (vsdeoldify/__init__.py:1959-2127) ------------------------------------------------------------------------------------------------
+DEF_MIN_FREQ, DEF_NUM_RF_FRAMES = 10, 10                                                           # vsslib/constants.py:61, 66
+
+
+def restore_video_params(method, ex_model, ref_merge, ref_weight, ref_thresh, ref_freq):
+    """the parameter defaulting of __init__.py:2066-2083 -> (ref_thresh, ref_freq, ref_weight, merge): merge = False: the scenes of clip_ref are its
+    references, weight 1.0 and no clip_sc; merge = True (method 5 with ref_merge > 0): every clip_ref frame is a reference and clip_sc holds its scenes"""
+    from . import scdetect
+    if ref_thresh is None or ref_thresh == 0:
+        ref_thresh = scdetect.DEF_THRESHOLD
+    if ref_freq is None or ref_freq == 0:
+        ref_freq = DEF_MIN_FREQ if ex_model == 2 else 0
+    if ref_merge == 0 or method in (2, 6):
+        return ref_thresh, ref_freq, 1.0, False
+    if ref_weight is None or ref_weight == 0:
+        ref_weight = _REFMERGE_WEIGHT[ref_merge]
+    return ref_thresh, ref_freq, ref_weight, True
+
+
+def HAVC_restore_video(clip=None, clip_ref=None, method=6, render_speed='medium', ex_model=0, ref_merge=0, ref_weight=None, ref_thresh=None, ref_freq=None,
+                       ref_norm=False, max_memory_frames=0, render_vivid=True, encode_mode=0, encode_first=True, torch_dir=None, **harness):
+    """vsdeoldify/__init__.py:1959-2127: the colours of a reference VIDEO of the same film (clip_ref: the same frames, any size) moved onto the B&W master
+    `clip` with ColorMNet (ex_model 0) or DeepRemaster (ex_model 2).  clip_ref of another size is brought to the clip's with the library's Spline36 (zimg's
+    there).  Method 6 (or ref_merge 0): the reference frames are the scene changes of clip_ref (threshold ref_thresh, default 0.10; frequency ref_freq,
+    default 10 for DeepRemaster and 0 otherwise; ref_norm).  Method 5 with ref_merge > 0: every clip_ref frame is a reference, the scenes of clip_ref
+    become clip_sc, and the frames are blended with their clip_ref frame at ref_weight (default [0, .3, .4, .5, .6, .7][ref_merge]).
+    ex_model 0 is HAVC_deepex's ColorMNet loop (no colormap / dark / smooth); render_vivid reaches ColorMNet unchanged (memory reset at every reference
+    update), also with max_memory_frames > 0, where HAVC_deepex alone switches it off.  render_speed is checked for every ex_model, as there.  ex_model 2 is vs_deepremaster -> vs_sc_remaster_colorize
+    (vsmodels.py:164-178, remaster/__init__.py:40-200): max_memory_frames (default 10, at least 4) stills in the window, batches of 2 frames at the
+    inference size (Spline64), the stills taken from clip_ref where clip_sc (or clip_ref's own scenes) flags them (remaster_render.RemasterClipRender);
+    with 0 < ref_weight < 1 and a clip_sc EVERY coloured frame is blended with its clip_ref frame (Pillow LANCZOS to the inference size); Spline64 back
+    with the clip's luma, and the luma once more (vs_recover_clip_luma, :2125).  ndarray in -> ndarray out; DeviceImage operands stay in HBM.
+    encode_first is accepted and ignored (it chooses a second server process there).  Refused, not approximated: ex_model 1 (Deep-Exemplar: not built),
+    ex_model 2 with render_vivid=True (vs_tweak: zimg), encode_mode 2.  `harness` = keyword-only extras of this library: state_dict / network (ColorMNet)
+    or state_dict / model (DeepRemaster) instead of the weight files, device_index, luma_range (HAVC_SceneDetect's), frame_mindim / ref_minedge
+    (DeepRemaster's sizes, 320 / 256 in the reference), debug (a dict that receives "scenes", "clip_sc", "ref_weight", "clip_ref": the resized clip_ref,
+    and the ColorMNet loop's "ref_small")."""
+    for c in (clip, clip_ref):
+        if c is None or not (is_device(c) or isinstance(c, np.ndarray)):
+            raise HAVCError("HAVC_restore_video: this is not a clip")
+    unknown = set(harness) - {"state_dict", "network", "model", "device_index", "luma_range", "frame_mindim", "ref_minedge", "debug"}
+    if unknown:
+        raise TypeError(f"HAVC_restore_video: unexpected keyword arguments {sorted(unknown)}")
+    if method not in (5, 6):
+        raise HAVCError("HAVC: Video restore is supported only with methods: 5, 6")                 # __init__.py:2048
+    if ex_model not in (0, 1, 2):
+        raise HAVCError("HybridAVC: unknown exemplar model id: " + str(ex_model))                  # :2120
+    if ex_model == 1:
+        raise NotImplementedError("HAVC_restore_video: ex_model 1 (Deep-Exemplar) is not built: ColorMNet (0) and DeepRemaster (2) are, DESIGN.md section 7")
+    if ex_model == 2 and render_vivid:
+        raise NotImplementedError("HAVC_restore_video: render_vivid is vs_tweak (a zimg YUV420 round trip): not in this harness")
+    if encode_mode == 2:
+        raise NotImplementedError("HAVC_restore_video: encode_mode = 2 is not built; 0 and 1 both run in process, as DeepExColorMNet does")
+    if encode_mode not in (0, 1):
+        raise HAVCError("HAVC_restore_video: encode_mode must be 0, 1 or 2")
+    if ref_merge not in range(6):
+        raise HAVCError("HAVC_restore_video: ref_merge must be in range [0-5]")
+    if not isinstance(render_speed, str):
+        raise HAVCError("HAVC_restore_video: render_speed must be a string")
+    from .colormnet_render import DEEPEX_SIZES
+    if render_speed.lower() not in DEEPEX_SIZES:                                                  # get_deepex_size runs before the model switch: every ex_model
+        raise HAVCError("HAVC_deepex: unknown render_speed ->" + render_speed)                     # deepex/__init__.py:50-83 (the same four names for ex_model 2)
+    clip, single = _as_clip(clip)
+    clip_ref, _ = _as_clip(clip_ref)
+    n, h, w = clip.shape[:3]
+    if clip_ref.shape[0] != n:
+        raise HAVCError(f"HAVC_restore_video: clip_ref has {clip_ref.shape[0]} frames, clip has {n}")
+    ref_thresh, ref_freq, ref_weight, merge = restore_video_params(method, ex_model, ref_merge, ref_weight, ref_thresh, ref_freq)
+    # ---- everything below touches the GPU ----
+    from . import scdetect
+    device_index, debug = harness.get("device_index", 0), harness.get("debug")
+    engine = dx = None
+    if ex_model == 0:
+        from .colormnet_render import DeepExColorMNet
+        dx = DeepExColorMNet(vid_length=n, render_speed=render_speed, enable_resize=False, render_vivid=render_vivid, max_memory_frames=max_memory_frames,
+                             frame_propagate=False, project_dir=torch_dir, state_dict=harness.get("state_dict"), device_index=device_index,
+                             network=harness.get("network"))
+        ctx = dx.ctx
+    else:
+        from .remaster_render import DEF_MIN_RF_FRAMES, RemasterClipRender, resize_for_inference_size
+        memory_size = max(max_memory_frames or DEF_NUM_RF_FRAMES, DEF_MIN_RF_FRAMES)              # vsmodels.py:167-170
+        engine = RemasterClipRender(device_index=device_index, ref_minedge=harness.get("ref_minedge", 256), ref_buffer_size=memory_size, length=2,
+                                    state_dict=harness.get("state_dict"), model=harness.get("model"))
+        ctx = engine._ctx()
+    try:
+        if tuple(clip_ref.shape[1:3]) != (h, w):
+            clip_ref = spline36(ctx, clip_ref, w, h)                                               # :2057-2058
+        coeffs = scdetect.LUMA_FULL if harness.get("luma_range", "limited") == "full" else scdetect.LUMA_LIMITED
+        detected = scdetect.scene_detect(ctx, clip_ref, threshold=ref_thresh, frequency=ref_freq, frame_norm=ref_norm, coeffs=coeffs)
+        if merge:
+            scenes, clip_sc = scdetect.scene_detect(ctx, clip_ref, threshold=0, frequency=1, coeffs=coeffs), detected      # :2082-2083
+        else:
+            scenes, clip_sc = detected, None
+        if debug is not None:
+            debug.update(scenes=scenes, clip_sc=clip_sc, ref_weight=ref_weight, clip_ref=clip_ref)
+        if ex_model == 0:
+            return _colormnet_clip(dx, clip, clip_ref, scenes, clip_sc, ref_weight, single, None, debug)
+        fw, fh = resize_for_inference_size(w, h, harness.get("frame_mindim", 320))
+        host_in = not is_device(clip)
+        dclip = DeviceImage.from_numpy(ctx, clip) if host_in else clip
+        engine.load_clip_ref(clip_ref, (clip_sc if clip_sc is not None else scenes).scene_change_prev)       # remaster/__init__.py:109-112
+        merge_weight = ref_weight if clip_sc is not None else 1.0                                  # :177
+        small = spline64(ctx, dclip, fw, fh)
+        colored = DeviceImage(ctx, small.shape)
+        for n0 in range(0, n, 2):
+            n1 = min(n0 + 2, n)
+            colored.frames(n0, n1).copy_from(engine.process_clip_frames(small.frames(n0, n1), n0, min(n0 + 1, n - 1), merge_weight))
+        out = spline64(ctx, colored, w, h, luma_from=dclip)
+        out = F.chroma_post_process_np(ctx, out.as_rows(), dclip.as_rows()).reshaped(out.shape)    # vs_recover_clip_luma once more, :2125
+        if host_in:
+            out = out.numpy()
+            return out[0] if single else out
+        ctx.synchronize()
+        return out.reshaped(out.shape[1:]) if single else out
+    finally:
+        if engine is not None:
+            engine.close()

@@ -6,6 +6,9 @@ addMergin (remaster_utils.py:46-59), the window rule (ref_buffer_adjust: at most
 What differs is where the stills' features live: the reference pushes every still of the window through reffeatnet1 / reffeatnet2 on every call; here a
 still is encoded once, when it enters the window, into a slot of the reference ring (remaster_net.RemasterSession), and an advance overwrites the slot of
 the oldest still.  Both are exact: the two stacks are per-frame, and a softmax does not depend on the order of its keys.
+
+RemasterClipRender / ClipReferenceWindow are the clip mode (RemasterColorizer, remaster_render.py:51-277; HAVC_restore_video with ex_model = 2): the stills
+are the frames of a reference clip that scene-change flags mark, found by scanning the flags lazily in chunks of 500 frames.
 """
 import math
 import os
@@ -18,8 +21,9 @@ from .remaster_net import RemasterColorNet, RemasterSession
 from .render import get_context
 
 DEF_MAX_RF_FRAMES, DEF_MIN_RF_FRAMES, DEF_FUTURE_FRAME_WEIGHT = 200, 4, 0.5       # vsslib/constants.py:65-74
+DEF_MAX_BUFFER_SIZE = 500                                                          # vsslib/constants.py:68: frames per scan for reference frames
 IMG_EXTENSIONS = ('.png', '.PNG', '.jpg', '.JPG', '.jpeg', '.JPEG', '.ppm', '.PPM', '.bmp', '.BMP')
-BICUBIC = 3
+LANCZOS, BICUBIC = 1, 3
 
 
 def get_ref_num(filename):
@@ -85,6 +89,46 @@ class ReferenceWindow:
     def numbers(self):
         """frame numbers of the stills in the window, in the reference's order (oldest first)"""
         return [self.nums[i] for i in sorted(self.slots)]
+
+
+class ClipReferenceWindow(ReferenceWindow):
+    """The reference list of RemasterColorizer (clip mode, remaster_render.py:122-231): the frames whose _SceneChangePrev flag is 1, found by scanning
+    the flags lazily in chunks of max_buffer_size frames.  get_clip_ref_list: the first scan covers min(n, 500) frames and up to ten extensions follow
+    while fewer references than the buffer size are known; fewer than DEF_MIN_RF_FRAMES then raise (the message says "at least 2", as there).  The
+    window size (ref_storage_size) is fixed from what that found.  ref_buffer_adjust: every call first extends the list once when frame_n >=
+    clip_last_frame - clip_buffer_size, then applies the window rule of ReferenceWindow with the count known at that moment.  fast_refs (ref_step in
+    2..4) is never on through HAVC_restore_video and is not built."""
+
+    def __init__(self, flags, ref_buffer_size, max_buffer_size=DEF_MAX_BUFFER_SIZE):
+        self.flags = flags                                   # _SceneChangePrev per frame of clip_sc: anything indexable with a length
+        self.max_buffer_size = max_buffer_size
+        self.clip_total_frames = len(flags)
+        self.clip_buffer_size = min(self.clip_total_frames, max_buffer_size)
+        self.nums = [i for i in range(self.clip_buffer_size) if flags[i] == 1]
+        self.clip_last_frame = self.clip_buffer_size - 1
+        for _ in range(10):
+            if len(self.nums) < ref_buffer_size and self.clip_last_frame < self.clip_total_frames - 1:
+                self.extend()
+            else:
+                break
+        if len(self.nums) < DEF_MIN_RF_FRAMES:
+            from .havc import HAVCError
+            raise HAVCError(f"RemasterColorizer(): number of reference frames must be at least 2, found  {len(self.nums)}")   # HAVC_LogMessage joins with a blank
+        super().__init__(self.nums, ref_buffer_size)
+
+    def extend(self):
+        """extend_clip_ref_list: the flags of the next max_buffer_size frames"""
+        if self.clip_last_frame == self.clip_total_frames - 1:
+            return
+        num_frames = min(self.clip_total_frames - self.clip_last_frame - 1, self.max_buffer_size)
+        batch_size = self.clip_last_frame + num_frames + 1
+        self.nums.extend(i for i in range(self.clip_last_frame + 1, batch_size) if self.flags[i] == 1)
+        self.clip_last_frame = batch_size - 1
+
+    def advance(self, frame_n):
+        if frame_n >= self.clip_last_frame - self.clip_buffer_size:
+            self.extend()
+        return super().advance(frame_n)
 
 
 class RemasterRender:
@@ -217,3 +261,86 @@ class RemasterRender:
             out.frame(0).copy_from(tmp.frame(0))
             self.ctx.synchronize()                  # src / tmp go back to the pool when this returns
         return out
+
+
+class RemasterClipRender(RemasterRender):
+    """RemasterColorizer (remaster_render.py:51-277): RemasterRender with its stills taken from a reference CLIP -- the frames of clip_ref that the
+    scene-change flags of clip_sc mark (ClipReferenceWindow).  clip_ref is a u8 [n][h][w][3] array or a DeviceImage; the stills of a device-resident
+    clip_ref are resized (Pillow BICUBIC), pasted on black and encoded without leaving HBM.  The ring of encoded stills is RemasterRender's."""
+
+    _clip_ref = _still = None
+
+    def load_clip_ref(self, clip_ref, flags):
+        """load_clip_ref: flags = _SceneChangePrev per frame of clip_sc (clip_ref's own scenes when the caller has no clip_sc).  Returns the number of
+        references the first scans found."""
+        if not is_device(clip_ref):
+            clip_ref = np.ascontiguousarray(clip_ref, dtype=np.uint8)
+        if clip_ref.ndim != 4 or clip_ref.shape[3] != 3 or len(flags) != clip_ref.shape[0]:
+            raise ValueError(f"RemasterClipRender.load_clip_ref: clip_ref [n, h, w, 3] with one flag per frame, got {tuple(clip_ref.shape)} and {len(flags)} flags")
+        self._close_session()
+        self.window = ClipReferenceWindow(flags, self.ref_buffer_size)
+        h, w = clip_ref.shape[1:3]
+        self.target_w, self.target_h = target_size(w, h, self.ref_minedge)
+        self._clip_ref = clip_ref
+        return len(self.window.nums)
+
+    def _ref_image(self, idx):
+        n = self.window.nums[idx]
+        if not is_device(self._clip_ref):
+            return np.ascontiguousarray(self.add_margin(self._clip_ref[n]))
+        self._still = self._add_margin_dev(self._clip_ref.frame(n))          # alive until the (blocking) encode has run
+        return self._still.ptr
+
+    def _add_margin_dev(self, frame):
+        """addMergin on a device frame: the same resize entry point on device operands, a pitched device copy for the paste"""
+        ctx = self._ctx()
+        h, w = frame.shape[:2]
+        g = margin_geometry(w, h, self.target_w, self.target_h)
+        if g is None:
+            return frame
+        rw, rh, xp, yp = g
+        small = DeviceImage(ctx, (rh, rw, 3))
+        nat.check(ctx.lib.havc_pil_resize(ctx.h, frame.ptr, w, h, small.ptr, rw, rh, BICUBIC), ctx.h)
+        out = DeviceImage(ctx, (self.target_h, self.target_w, 3))
+        nat.check(ctx.lib.havc_dev_memset(ctx.h, out.ptr, 0, out.nbytes), ctx.h)
+        x0, y0, x1, y1 = max(xp, 0), max(yp, 0), min(xp + rw, self.target_w), min(yp + rh, self.target_h)
+        if x1 > x0 and y1 > y0:
+            nat.check(ctx.lib.havc_dev_copy_2d(ctx.h, out.ptr.value + (y0 * self.target_w + x0) * 3, self.target_w * 3,
+                                               small.ptr.value + ((y0 - yp) * rw + (x0 - xp)) * 3, rw * 3, (x1 - x0) * 3, y1 - y0), ctx.h)
+        ctx.synchronize()                                                     # `small` goes back to the pool when this returns
+        return out
+
+    def process_clip_frames(self, frames, first_frame, last_frame_idx, merge_weight=1.0):
+        """color_remaster / color_merge_remaster (remaster/__init__.py:123-173): process_frames on the frames first_frame.. of the clip; with
+        0 < merge_weight < 1 every coloured frame is blended (Image.blend) with its own clip_ref frame, brought to its size with Pillow LANCZOS."""
+        out = self.process_frames(frames, last_frame_idx)
+        if not 0 < merge_weight < 1:
+            return out
+        from . import imfilters as F
+        ctx, dev = self._ctx(), is_device(out)
+        n, H, W = out.shape[:3]
+        cr = self._clip_ref
+        ref = cr.frames(first_frame, first_frame + n) if is_device(cr) else cr[first_frame:first_frame + n]
+        if tuple(ref.shape[1:3]) != (H, W):
+            ref = lanczos_resize(ctx, ref, W, H, device=dev)                  # the batch's frames in one call: one pair of coefficient tables
+        if dev:
+            ref = ref if is_device(ref) else DeviceImage.from_numpy(ctx, ref)
+            merged = F.blend_np(ctx, out, ref, merge_weight)                  # per pixel: the batch as one tall image
+            ctx.synchronize()                                                 # `ref` goes back to the pool when this returns
+            return merged
+        return F.blend_np(ctx, out.reshape(n * H, W, 3), np.ascontiguousarray(ref).reshape(n * H, W, 3), merge_weight).reshape(out.shape)
+
+
+def lanczos_resize(ctx, img, w, h, device=None):
+    """Pillow Image.resize((w, h), LANCZOS) of one u8 frame [h][w][3] or of n frames [n][h][w][3] in one call, host or device operand; device=True / False
+    chooses where the result lives (default: where the operand is)"""
+    dev_in = is_device(img)
+    device = dev_in if device is None else device
+    if not dev_in:
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+    n = img.shape[0] if img.ndim == 4 else 1
+    shape = (n, h, w, 3) if img.ndim == 4 else (h, w, 3)
+    out = DeviceImage(ctx, shape) if device else np.empty(shape, np.uint8)
+    nat.check(ctx.lib.havc_pil_resize_n(ctx.h, img.ptr if dev_in else nat.as_ptr(img), img.shape[-2], img.shape[-3],
+                                        out.ptr if device else nat.as_ptr(out), w, h, LANCZOS, n), ctx.h)
+    return out
