@@ -547,6 +547,41 @@ int havc_equalize_clip(havc_ctx* ctx, const uint8_t* src, uint8_t* dst, const ha
  * Image.blend gets for method 0 / for methods 1 and 2 (-1: the equalised frame as it is), out[4..6] = rgb_balance's gains as float32 (1 when chan_sums or
  * rgb_factor is NULL).  sum_y: sum of cv2's Y over the frame; chan_sums: the three channel sums. */
 int havc_equalize_frame_params(int64_t sum_y, const int64_t* chan_sums, int64_t n_pixels, int range_tv, const double* rgb_factor, double* out);
+/* HAVC_retinex (vsdeoldify/__init__.py:1073-1101 -> vsslib/vsretinex.py:25-88) on a whole clip [n_frames][height][width][3]: multi-scale Retinex with colour
+ * preservation (MSRCP) between the reference's luma gate and luma blend, in one enqueue sequence of seven launches per CHUNK of frames; nothing comes back to
+ * the host in between.  The reference calls the retinex.MSRCP plugin, which cannot be executed where the fixtures are made: its pixel work is restated from
+ * the published algorithm (Petro / Sbert / Morel, IPOL 2014, with the Young - van Vliet recursive Gaussian) -- an UNPINNED stand-in; tests/retinex_util.py
+ * is its definition.  Per frame, float64 in a stated order, no FMA: with (sF, sR) = (0, 255) when fulls else (16, 219) and (dF, dR) likewise from fulld,
+ *   I = (R + G + B - 3 sF) * (1.0 / (3 sR));  per sigma the recursive Gaussian g of I (rows, then columns; forward and backward sweep, each started from
+ *   the line's first value);  P = product over the sigmas of (g <= 0 ? 1 : I / g + 1);  O = log(P) / n_sigmas;  a 4096-bin histogram of O between the
+ *   frame's extremes gives lo / hi where the running count from either end first exceeds (int)(n_pixels * 0.001 + 0.5);  O' = clamp((O - lo) * (1.0 / (hi - lo)),
+ *   0, 1), or I when the frame has no range;  gain = O' / I (1 when I <= 0), at most sR / (max(R, G, B) - sF);  out = clamp(floor((c - sF) * gain *
+ *   (dR / sR) + dF + 0.5), 0, 255).
+ * Around it, the reference's Python (pinned by tests/golden/retinex.npz): f_luma as in havc_equalize_clip, from the INPUT frame with range_tv; a frame
+ * outside luma_dark <= f_luma <= luma_bright comes back byte for byte as it went in; with blend != 0 and f_luma < 0.40 the result is Pillow-blended over
+ * the input with image_luma_blend(.., 0.40, 0.90, 0.25, 3.0).  The reference passes fulls = range_tv_in and fulld = range_tv_out (vsretinex.py:59).
+ * The recursions, the planes they run on and the MSR product are float64.  Scratch is bounded by the chunk: n_sigmas float64 planes per frame of the chunk
+ * plus a 16 KiB histogram and a record per frame. */
+typedef struct havc_retinex_params {
+    int width, height, n_frames;  /* at most 2^28 pixels per frame */
+    int n_sigmas;                 /* 1..8 */
+    double sigma[8];              /* each in [0.5, 10000] */
+    double luma_dark, luma_bright;
+    int fulls, fulld;             /* != 0: full range (0..255); 0: limited (16..235) */
+    int range_tv, blend;          /* range_tv: f_luma's range (the reference's range_tv_in) */
+    int chunk_frames;             /* frames per enqueue sequence; 0 = the library's choice (enough lines to fill the chip, at most 2 GiB of planes) */
+    int reserved;
+} havc_retinex_params;
+/* src, dst: host or device pointers like every filter here; dst must not be src.  Device operands: the call only enqueues.  tap: NULL, or (for the tests)
+ * room for n_frames * (n_sigmas + 1) planes of height * width doubles, host or device: per frame the n_sigmas Gaussian planes, then the product P.
+ * Integer sums, integer atomics on ordered bit patterns and stated float sequences throughout: the bytes are identical from run to run.  A NULL pointer,
+ * dst == src, a non-positive size, n_sigmas outside 1..8, a sigma outside [0.5, 10000], a NaN bound, chunk_frames < 0: HAVC_E_INVALID, nothing runs. */
+int havc_retinex_clip(havc_ctx* ctx, const uint8_t* src, uint8_t* dst, const havc_retinex_params* params, double* tap);
+/* the per-frame scalars of the call above, on the host (no context, no GPU): out[0] = f_luma, out[1] = gate (0 / 1), out[2] = the weight Image.blend gets
+ * (-1: no blend).  sum_y: sum of cv2's Y over the frame. */
+int havc_retinex_frame_params(int64_t sum_y, int64_t n_pixels, int range_tv, double luma_dark, double luma_bright, int blend, double* out);
+/* the recursive Gaussian's coefficients of one sigma in [0.5, 10000], on the host: out4 = {B, B1, B2, B3} */
+int havc_retinex_coefficients(double sigma, double* out4);
 /* the per-pixel half of luma_adjusted_levels (vsslib/imfilters.py:335-372): cv2 RGB->YUV, Y' = lut[Y], YUV->RGB.  The caller
  * derives the 256-entry table from havc_image_luma exactly like the reference (vsdeoldify_amd/imfilters.py). */
 int havc_luma_lut(havc_ctx* ctx, const uint8_t* img, const uint8_t* lut256, uint8_t* out, int width, int height);

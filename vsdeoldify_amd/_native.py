@@ -88,6 +88,13 @@ class EqualizeParams(C.Structure):
                 ("balance_weight", C.c_double), ("rgb_factor", C.c_double * 3), ("lut_in", C.c_uint8 * 256), ("lut_out", C.c_uint8 * 256)]
 
 
+class RetinexParams(C.Structure):
+    """`havc_retinex_params` (include/havc_mi355.h): clip size, sigmas, gate bounds, ranges, blend and chunk size of havc_retinex_clip"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int), ("n_sigmas", C.c_int), ("sigma", C.c_double * 8),
+                ("luma_dark", C.c_double), ("luma_bright", C.c_double), ("fulls", C.c_int), ("fulld", C.c_int), ("range_tv", C.c_int),
+                ("blend", C.c_int), ("chunk_frames", C.c_int), ("reserved", C.c_int)]
+
+
 class RecoverParams(C.Structure):
     """`havc_recover_params` (include/havc_mi355.h): clip size, first frame number and the arguments of ChromaRetentionMerge's selectors (havc_recover_color_clip)"""
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int), ("first_frame", C.c_int), ("sat", C.c_double), ("tht", C.c_int),
@@ -170,6 +177,9 @@ SYMBOLS = [
     ("havc_scene_ssim_value", _D, [_I, _I, _I, _I, _I]),
     ("havc_equalize_clip", _I, [_P, _P, _P, _P]),
     ("havc_equalize_frame_params", _I, [C.c_int64, _P, C.c_int64, _I, _P, _P]),
+    ("havc_retinex_clip", _I, [_P, _P, _P, _P, _P]),
+    ("havc_retinex_frame_params", _I, [C.c_int64, C.c_int64, _I, _D, _D, _I, _P]),
+    ("havc_retinex_coefficients", _I, [_D, _P]),
     ("havc_luma_lut", _I, [_P, _P, _P, _P, _I, _I]),
     ("havc_restore_color_gradient", _I, [_P, _P, _P, _P, _I, _I, _D, _I, _D, _D, _I, _I]),
     ("havc_recover_color_clip", _I, [_P, _P, _P, _P, _P]),

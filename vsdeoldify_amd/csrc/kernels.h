@@ -224,6 +224,20 @@ struct RecoverArgs {
     int luma_blocks, apply_blocks;   // blocks per frame of the two launches, set by launch_recover_color
 };
 int launch_recover_color(const uint8_t* gray, const uint8_t* color, uint8_t* out, unsigned long long* sums, RecoverArgs a, hipStream_t s);
+// retinex.hip: HAVC_retinex = multi-scale Retinex (MSRCP) on a chunk of a clip [n][h][w][3] (vsslib/vsretinex.py:52-88; the plugin's pixel work restated from
+// its published algorithm).  All of a chunk's frames and sigmas go through every launch together.
+struct RetArgs {
+    int n, h, w, ns;              // frames of the chunk, frame size, number of sigmas (1..8)
+    int sF, sR, dF, dR;           // source / destination range: (0, 255) full, (16, 219) limited
+    int range_tv, blend;
+    double luma_dark, luma_bright;
+    double coef[8][4];            // B, B1, B2, B3 per sigma (ret_coefficients)
+    int blocks_per_frame;         // set by launch_retinex
+};
+size_t retinex_record_bytes(int n);                  // the per-frame records and histograms of n frames (zero-filled by the caller)
+// planes: n * ns float64 planes of h * w; rec: retinex_record_bytes(n) bytes, zero-filled on the same stream in front of the call; tap_g / tap_p (both or
+// neither, device memory): the n * ns Gaussian planes and the n MSR product planes, for the tests
+int launch_retinex(const uint8_t* src, uint8_t* dst, double* planes, void* rec, double* tap_g, double* tap_p, RetArgs a, hipStream_t s);
 // separable polyphase resample of interleaved u8 RGB (tap tables from the host; Spline64 = harness stand-in
 // for zimg resize.Spline64).  orig != null fuses chroma_post_process (luma of orig, chroma of the resampled).
 int launch_resize_passes(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, int n_frames, float* tmp,
@@ -273,6 +287,7 @@ void preload_recover();
 void preload_scdetect();
 void preload_scfilter();
 void preload_equalize();
+void preload_retinex();
 void preload_ddcolor();
 void preload_colormnet();
 void preload_colormnet_net();

@@ -3,6 +3,7 @@
 #include "scdetect_ops.h"
 #include "scfilter_ops.h"
 #include "equalize_ops.h"
+#include "retinex_ops.h"
 
 extern "C" {
 
@@ -380,6 +381,83 @@ int havc_equalize_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const havc
     const int e = launch_equalize(d_src, d_dst, c->scratch[SCR_SMALL], a, c->stream);
     c->stats.launches += a.balance ? 3 : 2;
     if (e) return hip_fail(c, (hipError_t)e, "equalize_clip");
+    return stage_out(c, dst, d_dst, cb, host);
+}
+
+// ---- HAVC_retinex: multi-scale Retinex (MSRCP) on a clip, chunk by chunk (retinex.hip) ----
+static_assert(sizeof(havc_retinex_params) == 120, "havc_retinex_params layout");
+static_assert(sizeof(RetFrameRec) == 56, "RetFrameRec layout");
+
+int havc_retinex_coefficients(double sigma, double* out4) {
+    if (!out4 || !(sigma >= 0.5 && sigma <= 10000.0)) return HAVC_E_INVALID;
+    ret_coefficients(sigma, out4);
+    return HAVC_OK;
+}
+
+int havc_retinex_frame_params(int64_t sum_y, int64_t n_pixels, int range_tv, double luma_dark, double luma_bright, int blend, double* out) {
+    if (sum_y < 0 || n_pixels <= 0 || !out) return HAVC_E_INVALID;
+    const double fl = eq_f_luma((unsigned long long)sum_y, n_pixels, range_tv);
+    out[0] = fl;
+    out[1] = ret_gate(fl, luma_dark, luma_bright) ? 1.0 : 0.0;
+    out[2] = (double)ret_blend_weight(fl, blend);
+    return HAVC_OK;
+}
+
+// Frames per chunk.  The recursions of a launch are rows x frames x sigmas (horizontal) or columns x frames x sigmas (vertical), one lane each; the step
+// is a dependent chain of one product and three sums behind seven issued instructions, so about two waves per SIMD keep a SIMD issuing: 256 CUs x 4
+// SIMDs x 2 waves x 64 lanes = 131072 lanes for the smaller of the two launches.  The planes of a chunk are capped at 2 GiB.
+static int retinex_chunk_frames(const havc_retinex_params* p) {
+    if (p->chunk_frames > 0) return std::min(p->chunk_frames, p->n_frames);
+    const int64_t lanes = (int64_t)std::min(p->width, p->height) * p->n_sigmas;
+    const int64_t want = (131072 + lanes - 1) / lanes;
+    const int64_t cap = std::max<int64_t>(1, ((int64_t)2 << 30) / ((int64_t)p->width * p->height * p->n_sigmas * (int64_t)sizeof(double)));
+    return (int)std::max<int64_t>(1, std::min<int64_t>(std::min(want, cap), p->n_frames));
+}
+
+int havc_retinex_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const havc_retinex_params* p, double* tap) {
+    if (!c || !src || !dst || !p) return fail(c, HAVC_E_INVALID, "retinex_clip: bad args");
+    if (src == dst) return fail(c, HAVC_E_INVALID, "retinex_clip: dst must not be src (the blend and the gate read the input frame)");
+    if (p->n_frames <= 0 || p->width <= 0 || p->height <= 0 || (int64_t)p->width * p->height > ((int64_t)1 << 28))
+        return fail(c, HAVC_E_INVALID, "retinex_clip: bad clip size (at most 2^28 pixels per frame)");
+    if (p->n_sigmas < 1 || p->n_sigmas > RET_MAX_SIGMAS) return fail(c, HAVC_E_INVALID, "retinex_clip: n_sigmas must be 1..8");
+    for (int k = 0; k < p->n_sigmas; ++k)
+        if (!(p->sigma[k] >= 0.5 && p->sigma[k] <= 10000.0)) return fail(c, HAVC_E_INVALID, "retinex_clip: every sigma must be in [0.5, 10000]");
+    if (!(p->luma_dark == p->luma_dark) || !(p->luma_bright == p->luma_bright)) return fail(c, HAVC_E_INVALID, "retinex_clip: luma_dark / luma_bright is NaN");
+    if (p->chunk_frames < 0) return fail(c, HAVC_E_INVALID, "retinex_clip: chunk_frames must be >= 0");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    RetArgs a{};
+    a.h = p->height; a.w = p->width; a.ns = p->n_sigmas;
+    a.sF = p->fulls ? 0 : 16; a.sR = p->fulls ? 255 : 219;
+    a.dF = p->fulld ? 0 : 16; a.dR = p->fulld ? 255 : 219;
+    a.range_tv = p->range_tv != 0; a.blend = p->blend != 0;
+    a.luma_dark = p->luma_dark; a.luma_bright = p->luma_bright;
+    for (int k = 0; k < a.ns; ++k) ret_coefficients(p->sigma[k], a.coef[k]);
+    const int chunk = retinex_chunk_frames(p);
+    const size_t npix = (size_t)a.h * a.w, fb = npix * 3, cb = (size_t)p->n_frames * fb, pb = npix * sizeof(double);
+    int rc;
+    const uint8_t* d_src;
+    uint8_t* d_dst;
+    bool host;
+    if ((rc = stage_in(c, SCR_IN, src, cb, &d_src)) || (rc = stage_out_ptr(c, SCR_OUT, dst, cb, &d_dst, &host)) ||
+        (rc = ensure_scratch(c, SCR_SMALL, retinex_record_bytes(chunk))) || (rc = ensure_scratch(c, SCR_RETINEX_PLANES, (size_t)chunk * a.ns * pb)) ||
+        (tap && (rc = ensure_scratch(c, SCR_RETINEX_TAP, (size_t)chunk * (a.ns + 1) * pb)))) return rc;
+    double* d_planes = (double*)c->scratch[SCR_RETINEX_PLANES];
+    double* d_tap_g = tap ? (double*)c->scratch[SCR_RETINEX_TAP] : nullptr;
+    double* d_tap_p = tap ? d_tap_g + (size_t)chunk * a.ns * npix : nullptr;
+    for (int f0 = 0; f0 < p->n_frames; f0 += chunk) {
+        a.n = std::min(chunk, p->n_frames - f0);
+        HIP_TRY(c, hipMemsetAsync(c->scratch[SCR_SMALL], 0, retinex_record_bytes(a.n), c->stream));
+        const int e = launch_retinex(d_src + (size_t)f0 * fb, d_dst + (size_t)f0 * fb, d_planes, c->scratch[SCR_SMALL], d_tap_g, d_tap_p, a, c->stream);
+        c->stats.launches += 7;
+        if (e) return hip_fail(c, (hipError_t)e, "retinex_clip");
+        for (int f = 0; tap && f < a.n; ++f) {                   // per frame: the n_sigmas Gaussian planes, then the product plane
+            double* t = tap + (size_t)(f0 + f) * (a.ns + 1) * npix;
+            HIP_TRY(c, hipMemcpyAsync(t, d_tap_g + (size_t)f * a.ns * npix, a.ns * pb, hipMemcpyDefault, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(t + (size_t)a.ns * npix, d_tap_p + (size_t)f * npix, pb, hipMemcpyDefault, c->stream));
+        }
+    }
+    if (tap && !is_device_ptr(tap)) HIP_TRY(c, hipStreamSynchronize(c->stream));
     return stage_out(c, dst, d_dst, cb, host);
 }
 

@@ -70,6 +70,7 @@ enum ScratchSlot {
     SCR_IN2 = 1,                       // second operand: image b of a two-input filter; ColorMNet: qk / k / ab
     SCR_VIDEO = SCR_IN2,               //   DeOldify drivers: raw colour of the video model
     SCR_PIL_ROWS = SCR_IN2,            //   u8 row pass of a Pillow resize (havc_pil_resize, the Zhang / DDColor squash to S x S)
+    SCR_RETINEX_TAP = SCR_IN2,         //   havc_retinex_clip with a tap (tests only): a chunk's Gaussian and product planes on their way out
     SCR_OUT = 2,                       // result of a filter / resize / ColorMNet op on its way to the host; the host tiles of havc_tile_slice
     SCR_SECOND = SCR_OUT,              //   DeOldify drivers: raw colour of the second (stable / artistic) model
     SCR_SQUARE = SCR_OUT,              //   Zhang / DDColor: the frames squashed to the net's S x S input
@@ -79,8 +80,10 @@ enum ScratchSlot {
     SCR_PLANES = SCR_IN4,              //   planar entry points: the three planes of a frame, in and (u8) out
     SCR_IN5 = 5,                       // ColorMNet: qe (selection) / rel_b
     SCR_PLANES_OUT = SCR_IN5,          //   havc_ddcolor_frame_planar_f: the float / half planes on their way out
-    SCR_SMALL = 6,                     // small results and tables: luma sums, a 256-byte LUT, scene records, the equalisation workspace, a usage vector
+    SCR_SMALL = 6,                     // small results and tables: luma sums, a 256-byte LUT, scene records, the equalisation workspace, a usage vector,
+                                       // the Retinex records and histograms of a chunk
     SCR_RESIZE_ROWS = 7,               // fp32 rows between the two passes of the Spline64 resize
+    SCR_RETINEX_PLANES = SCR_RESIZE_ROWS,   //   havc_retinex_clip: the float64 Gaussian planes of a CHUNK of frames (n_sigmas per frame; bounded by the chunk)
     // 8-11: the pipelined host clip (havc_colorize_clip_host), double-buffered by batch parity; the ONE-SHOT ColorMNet reads reuse them
     SCR_CLIP_SRC = 8,                  // 8, 9: source batches, SCR_CLIP_SRC + (batch & 1)
     SCR_SIM = SCR_CLIP_SRC,            //   one-shot read: similarity map [B][N][HW]; havc_local_attention: the attention map

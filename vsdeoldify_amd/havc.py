@@ -11,6 +11,7 @@
     HAVC_export_reference_frames  vsdeoldify/__init__.py:3364-3385   HAVC_export_list_frames vsdeoldify/__init__.py:3387-3416   (the writers alone)
     HAVC_recover_clip_color vsdeoldify/__init__.py:2956-2992   (ChromaRetentionMerge on a clip: gradient and binary mask, chroma_resize through the library's Spline64)
     HAVC_restore_video vsdeoldify/__init__.py:1959-2127   (colour transfer from a reference video: ex_model 0 = ColorMNet, 2 = DeepRemaster's clip mode; methods 5, 6)
+    HAVC_retinex     vsdeoldify/__init__.py:1073-1101     (multi-scale Retinex, MSRCP, with the luma gate and blend of vs_retinex_fast; float64 Gaussians; retinex.py)
 
 Same names, argument lists, defaults, parameter normalisation, frame-size rule, model routing, combine dispatch
 (vsslib/mcomb.py:125-192) and error texts; a "clip" is a uint8 array [n, h, w, 3] (or one frame [h, w, 3], or a
@@ -49,6 +50,10 @@ contract; none of it can be executed where the fixtures are made
     and equalizeHist follow OpenCV's published algorithm (cv2 cannot be executed there either).  The gate, the f_luma roundings, the blend weights, Pillow's
     blend and rgb_balance's gains are the reference's Python, restated and pinned by tests/golden/equalize.npz.  Methods 4 (timecube plugin + LUT files) and
     5 (Retinex MSRCP plugin) and `chroma_resize=True` (a zimg round trip inside convert_format_RGB24) are refused.
+  * HAVC_retinex (vsdeoldify_amd/retinex.py has the details): the `retinex.MSRCP` plugin -> the published MSRCP algorithm (Petro / Sbert / Morel, IPOL 2014)
+    with the Young - van Vliet recursive Gaussian, float64, restated in tests/retinex_util.py -- the plugin cannot be executed where the fixtures are made.
+    The gate, the f_luma roundings, the blend weight, Pillow's blend and the arguments handed to the plugin are the reference's Python, restated and pinned
+    by tests/golden/retinex.npz.  `chroma_resize=True` is refused; method 5 of HAVC_bw_tune / HAVC_auto_levels is not routed here yet and stays refused.
 HAVC_clip_slice pads where the reference's std.CropAbs would leave the padded clip by one pixel (an odd width / height with overlap 0: VapourSynth
 raises there); every other geometry CropAbs refuses -- an overlap >= the base tile, a negative overlap -- is refused with HAVCError.
 
@@ -1089,6 +1094,27 @@ def HAVC_bw_tune(clip=None, bw_tune='Light', bw_method=0, luma_blend=True, range
     return _equalize_clip(clip, device_index, method=bw_method, strength=b_strength[bw_id], weight3=w_strength[bw_id], luma_blend=luma_blend,
                           range_tv=range_tv, range_tv_tables=bool(range_tv),
                           balance=(w_strength[bw_id], [r_factor[bw_id], g_factor[bw_id], b_factor[bw_id]]))       # :1328-1333
+
+
+# ---- HAVC_retinex (vsdeoldify/__init__.py:1073-1101 -> vsslib/vsretinex.py:25-88 vs_retinex / vs_retinex_fast) ----------------------------------------
+def HAVC_retinex(clip, luma_dark=0.20, luma_bright=0.80, sigmas=(25, 80, 250), range_tv_in=True, range_tv_out=True, blend=False, chroma_resize=False, *,
+                 device_index=0):
+    """vsdeoldify/__init__.py:1073-1101: multi-scale Retinex (MSRCP) that leaves dark and bright frames alone -- a frame whose f_luma lies outside
+    [luma_dark, luma_bright] comes back as it went in; with blend the result of a frame below 0.40 is blended over the input.  The plugin's pixel work is
+    a stand-in restated from its published algorithm (retinex.py says what is pinned and what is not).  One havc_retinex_clip call: seven launches per
+    chunk of frames, float64 Gaussians.  A frame or a clip; ndarray in -> ndarray out; DeviceImage in -> DeviceImage out (nothing leaves HBM, the call
+    only enqueues).  chroma_resize=True is refused."""
+    from . import retinex
+    if clip is None or not (is_device(clip) or isinstance(clip, np.ndarray)):
+        raise HAVCError("HAVC_retinex: this is not a clip")
+    retinex.check_args(tuple(clip.shape), sigmas, chroma_resize, clip.dtype if isinstance(clip, np.ndarray) else np.uint8)
+    clip, single = _as_clip(clip)
+    ctx = clip.ctx if is_device(clip) else get_context(device_index)
+    out = retinex.retinex_np(ctx, clip, **retinex.plugin_args(sigmas, range_tv_in, range_tv_out),                       # vsretinex.py:58-59
+                             luma_dark=luma_dark, luma_bright=luma_bright, range_tv=range_tv_in, blend=blend)          # :86-87
+    if single:
+        return out.reshaped(out.shape[1:]) if is_device(out) else out[0]
+    return out
 
 
 # ---- HAVC_DeepRemaster (vsdeoldify/__init__.py:2689-2735 -> remaster/__init__.py:203-307 vs_remaster_colorize) ----------------------------------------
