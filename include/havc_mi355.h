@@ -516,6 +516,34 @@ int havc_scene_ssim(havc_ctx* ctx, const uint8_t* clip, int n_frames, int width,
  * (sum x, sum y, sum x^2, sum y^2, sum x * y over the 49 samples) */
 int havc_scene_gray(int r, int g, int b);
 double havc_scene_ssim_value(int sx, int sy, int sxx, int syy, int sxy);
+/* HAVC_SceneDetectEdges (vsdeoldify/__init__.py:3227-3258 -> vsslib/vsscdetect_edge.py:168-182): the per-frame integers the reference's edge-masked detector
+ * reads of the small RGB clip [n_frames][height][width][3], in ONE launch.  The gray plane Y is havc_scene_stats'; every neighbourhood reflects at the
+ * image border (reflect-101, as often as needed; a side of 1 pixel reflects to itself).
+ *   kirsch  = max over the reference's four 3 x 3 matrices of min(|sum|, 255)
+ *   tcanny  = on E = round_half_up(sqrt(Y / 255) * 255) (float32): Gaussian of radius r = max(int(3 sigma + 0.5), 1), float32 weights exp(-x^2 / (2 sigma^2))
+ *             normalised by their sum, vertical pass then horizontal, taps added from -r to +r with every product and sum rounded to float32; Prewitt
+ *             gx = ((tr + r + br) - (tl + l + bl)) * 0.5, gy = ((tl + t + tr) - (bl + b + br)) * 0.5; int(sqrt(gx^2 + gy^2) + 0.5), at most 255
+ *   mask    = min(kirsch + tcanny, 255);   diff = |Y_n - Y_j|, j = n + offset for n < n_frames - offset, else n_frames - offset
+ * tests/scedges_util.py is the definition.  No plane is stored: gray is recomputed from the RGB bytes and everything else lives in LDS. */
+typedef struct havc_edge_params {
+    int width, height, n_frames;  /* width, height at most 16384 */
+    int offset;                   /* 1..25 and < n_frames */
+    int cr, cg, cb, bias;         /* as havc_scene_params */
+    double sigma;                 /* 0 < sigma <= 2.5 (radius at most 8); the reference uses 1.2 */
+} havc_edge_params;
+typedef struct havc_edge_rec {
+    int64_t sum_y;                /* sum of the frame's gray plane */
+    int64_t sad_prev;             /* sum of |Y_n - Y_max(n - 1, 0)|: what the misc.SCDetect stand-in reads */
+    int64_t sad_next;             /* sum of diff */
+    int64_t sum_masked;           /* sum of (diff * mask + 127) / 255 */
+} havc_edge_rec;
+/* clip: host or device pointer (a device clip is read in place).  out: n_frames records in HOST memory; the call blocks until they are there.  mask_tap:
+ * NULL, or room for n_frames * height * width mask bytes, host or device (for tests).  The sums are integers: bit-identical from run to run.  Anything
+ * outside the limits above, offset >= n_frames included: HAVC_E_INVALID, nothing runs. */
+int havc_scene_edge_stats(havc_ctx* ctx, const uint8_t* clip, const havc_edge_params* params, havc_edge_rec* out, uint8_t* mask_tap);
+/* the tables the call above hands its kernel, on the host (no context, no GPU): the 256-entry enhanced-plane table, the blur's 2 r + 1 weights (tap -r
+ * first; weights17 is zero-filled behind them) and r.  sigma outside (0, 2.5]: HAVC_E_INVALID. */
+int havc_scene_edge_tables(double sigma, uint8_t* enh256, float* weights17, int* radius);
 /* HAVC_bw_tune (vsdeoldify/__init__.py:1266-1339) and HAVC_auto_levels (:3150-3179 -> havc_utils.py:785-833) on a whole clip [n_frames][height][width][3]:
  * rgb_balance (havc_utils.py:1087-1145; with balance != 0) and rgb_equalizer (:836-1075), methods 0-3, in two launches (three with balance) that hand their
  * per-frame results on in device memory.

@@ -81,6 +81,12 @@ class SceneParams(C.Structure):
                 ("bias", C.c_int), ("normalize", C.c_int), ("reserved", C.c_int), ("tht_black", C.c_double), ("tht_white", C.c_double)]
 
 
+class EdgeParams(C.Structure):
+    """`havc_edge_params` (include/havc_mi355.h): clip size, offset, luma coefficients and blur sigma of havc_scene_edge_stats"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int), ("offset", C.c_int), ("cr", C.c_int), ("cg", C.c_int), ("cb", C.c_int),
+                ("bias", C.c_int), ("sigma", C.c_double)]
+
+
 class EqualizeParams(C.Structure):
     """`havc_equalize_params` (include/havc_mi355.h): clip size, method, merge weights, rgb_balance and the in / out tables of havc_equalize_clip"""
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int), ("method", C.c_int), ("luma_blend", C.c_int), ("range_tv", C.c_int),
@@ -103,6 +109,9 @@ class RecoverParams(C.Structure):
 
 # numpy mirror of `havc_scene_rec`: one record per frame
 SCENE_REC_DTYPE = np.dtype([("sum_y", "<i8"), ("sad", "<i8"), ("sum_raw", "<i8"), ("min_y", "<i4"), ("max_y", "<i4")], align=True)
+
+# numpy mirror of `havc_edge_rec`: one record per frame
+EDGE_REC_DTYPE = np.dtype([("sum_y", "<i8"), ("sad_prev", "<i8"), ("sad_next", "<i8"), ("sum_masked", "<i8")], align=True)
 
 
 class NativeLibraryError(RuntimeError):
@@ -175,6 +184,8 @@ SYMBOLS = [
     ("havc_scene_ssim", _I, [_P, _P, _I, _I, _I, _P, _I, _P]),
     ("havc_scene_gray", _I, [_I, _I, _I]),
     ("havc_scene_ssim_value", _D, [_I, _I, _I, _I, _I]),
+    ("havc_scene_edge_stats", _I, [_P, _P, _P, _P, _P]),
+    ("havc_scene_edge_tables", _I, [_D, _P, _P, _P]),
     ("havc_equalize_clip", _I, [_P, _P, _P, _P]),
     ("havc_equalize_frame_params", _I, [C.c_int64, _P, C.c_int64, _I, _P, _P]),
     ("havc_retinex_clip", _I, [_P, _P, _P, _P, _P]),

@@ -198,6 +198,18 @@ constexpr int SCF_SSIM_TILE = 32;     // window positions per block and directio
 int scene_ssim_tiles(int h, int w, int* tiles_x = nullptr, int* tiles_y = nullptr);
 int launch_scene_hist(const uint8_t* clip, const int* idx, int k, unsigned* out, int h, int w, hipStream_t s);
 int launch_scene_ssim(const uint8_t* clip, const int* pairs, int m, double* partial, double* out, int h, int w, hipStream_t s);
+// scedge.hip: the edge-masked scene statistics of a clip [n][h][w][3] (vsslib/vsscdetect_edge.py:168-182).  EdgeRec is the layout of havc_edge_rec.
+constexpr int EDGE_MAX_SIDE = 16384;  // width and height: keeps a wave's 32-bit partial sums exact (scedge.hip)
+struct EdgeRec { long long sum_y, sad_prev, sad_next, sum_masked; };
+struct EdgeStatsArgs {
+    int n, h, w, offset;          // 1 <= offset < n
+    int cr, cg, cb, bias;         // as SceneStatsArgs
+    int radius;                   // 1..8: the blur's radius; wt[0 .. 2 radius] its weights, tap -radius first
+    int blocks_per_frame, tiles_x, tiles_y;       // set by launch_scene_edge_stats
+    float wt[17];
+    uint8_t enh[256];             // the enhanced plane's table
+};
+int launch_scene_edge_stats(const uint8_t* clip, EdgeRec* rec, uint8_t* tap, EdgeStatsArgs a, hipStream_t s);   // rec: n zero-filled device records
 // equalize.hip: rgb_equalizer methods 0-3 (CLAHE / equalizeHist) with rgb_balance in front, on a clip [n][h][w][3] (vsdeoldify/havc_utils.py:836-1145)
 struct EqArgs {
     int n, h, w, method;          // method 0..3
@@ -286,6 +298,7 @@ void preload_tiles();
 void preload_recover();
 void preload_scdetect();
 void preload_scfilter();
+void preload_scedge();
 void preload_equalize();
 void preload_retinex();
 void preload_ddcolor();

@@ -2,6 +2,7 @@
 #include "runtime_internal.h"
 #include "scdetect_ops.h"
 #include "scfilter_ops.h"
+#include "scedge_ops.h"
 #include "equalize_ops.h"
 #include "retinex_ops.h"
 
@@ -325,6 +326,55 @@ int havc_scene_ssim(havc_ctx* c, const uint8_t* clip, int n_frames, int width, i
     c->stats.launches += 2;
     if (e) return hip_fail(c, (hipError_t)e, "scene_ssim");
     HIP_TRY(c, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HAVC_OK;
+}
+
+// ---- HAVC_SceneDetectEdges' per-frame statistics (scedge.hip) ----
+static_assert(sizeof(EdgeRec) == sizeof(havc_edge_rec) && sizeof(havc_edge_rec) == 32, "havc_edge_rec layout");
+static_assert(sizeof(havc_edge_params) == 40, "havc_edge_params layout");
+
+int havc_scene_edge_tables(double sigma, uint8_t* enh256, float* weights17, int* radius) {
+    if (!enh256 || !weights17 || !radius || !(sigma > 0.0 && sigma <= 2.5)) return HAVC_E_INVALID;
+    *radius = edge_radius(sigma);
+    for (int k = 0; k < EDGE_MAX_TAPS; ++k) weights17[k] = 0.f;
+    edge_weights(sigma, *radius, weights17);
+    edge_enhance_table(enh256);
+    return HAVC_OK;
+}
+
+int havc_scene_edge_stats(havc_ctx* c, const uint8_t* clip, const havc_edge_params* p, havc_edge_rec* out, uint8_t* mask_tap) {
+    if (!c || !clip || !p || !out) return fail(c, HAVC_E_INVALID, "scene_edge_stats: bad args");
+    if (p->width <= 0 || p->height <= 0 || p->n_frames <= 0 || p->width > EDGE_MAX_SIDE || p->height > EDGE_MAX_SIDE)
+        return fail(c, HAVC_E_INVALID, "scene_edge_stats: bad clip size (at most 16384 x 16384)");
+    if (p->offset < 1 || p->offset > 25) return fail(c, HAVC_E_INVALID, "scene_edge_stats: offset must be 1..25");
+    if (p->offset >= p->n_frames) return fail(c, HAVC_E_INVALID, "scene_edge_stats: offset must be smaller than the number of frames");
+    if (p->cr < 0 || p->cg < 0 || p->cb < 0 || p->bias < 0 || ((int64_t)p->cr + p->cg + p->cb) * 255 + p->bias >= ((int64_t)256 << 16))
+        return fail(c, HAVC_E_INVALID, "scene_edge_stats: luma coefficients must be >= 0 and keep Y = (cr*R + cg*G + cb*B + bias) >> 16 below 256");
+    if (!(p->sigma > 0.0 && p->sigma <= 2.5)) return fail(c, HAVC_E_INVALID, "scene_edge_stats: sigma must be in (0, 2.5]");
+    if (is_device_ptr(out)) return fail(c, HAVC_E_INVALID, "scene_edge_stats: the records are downloaded: out must be host memory");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    EdgeStatsArgs a{};
+    a.n = p->n_frames; a.h = p->height; a.w = p->width; a.offset = p->offset;
+    a.cr = p->cr; a.cg = p->cg; a.cb = p->cb; a.bias = p->bias;
+    a.radius = edge_radius(p->sigma);
+    edge_weights(p->sigma, a.radius, a.wt);
+    edge_enhance_table(a.enh);
+    const size_t pb = (size_t)a.n * a.h * a.w, cb = pb * 3, rb = (size_t)a.n * sizeof(EdgeRec);
+    int rc;
+    const uint8_t* d_clip;
+    uint8_t* d_tap = nullptr;
+    bool host_tap = false;
+    if ((rc = stage_in(c, SCR_IN, clip, cb, &d_clip)) || (rc = ensure_scratch(c, SCR_SMALL, rb)) ||
+        (mask_tap && (rc = stage_out_ptr(c, SCR_OUT, mask_tap, pb, &d_tap, &host_tap)))) return rc;
+    EdgeRec* d_rec = (EdgeRec*)c->scratch[SCR_SMALL];
+    HIP_TRY(c, hipMemsetAsync(d_rec, 0, rb, c->stream));
+    const int e = launch_scene_edge_stats(d_clip, d_rec, d_tap, a, c->stream);
+    c->stats.launches++;
+    if (e) return hip_fail(c, (hipError_t)e, "scene_edge_stats");
+    HIP_TRY(c, hipMemcpyAsync(out, d_rec, rb, hipMemcpyDeviceToHost, c->stream));
+    if (mask_tap && (rc = stage_out(c, mask_tap, d_tap, pb, host_tap))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return HAVC_OK;
 }

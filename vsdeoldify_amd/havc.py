@@ -4,6 +4,7 @@
     HAVC_ddeoldify   vsdeoldify/__init__.py:3612-3628     ddeoldify        vsdeoldify/__init__.py:3642-3653
     HAVC_stabilizer  vsdeoldify/__init__.py:2748-2873     HAVC_clip_slice / HAVC_clip_reconstruct (+ ClipTiles)  vsdeoldify/__init__.py:2886-2945
     HAVC_SceneDetect vsdeoldify/__init__.py:3191-3225     (-> scdetect.SceneInfo: arrays carry no frame props)
+    HAVC_SceneDetectEdges vsdeoldify/__init__.py:3227-3258   (the edge-masked detector + its SSIM / histogram filter -> scdetect_edge.EdgeSceneInfo; scdetect_edge.py)
     HAVC_deepex      vsdeoldify/__init__.py:1421-1735     (ex_model 0 = ColorMNet, method 0; `scenes=` is the SceneInfo the reference reads off clip_ref's props)
     HAVC_bw_tune     vsdeoldify/__init__.py:1266-1339     HAVC_auto_levels vsdeoldify/__init__.py:3150-3179   (methods 0-3: CLAHE / equalizeHist; equalize.py)
     HAVC_DeepRemaster vsdeoldify/__init__.py:2689-2735    (mode 0: reference stills from a directory; remaster_render.RemasterRender; fast mode only)
@@ -21,7 +22,7 @@ behind `HAVC_colorizer` (models and nets are built once and reused between calls
 What only VapourSynth can do stays there and is REFUSED here instead of being approximated: `vs_tweak` (deoldify / ddcolor
 sat / hue other than 1 / 0, `luma_mask_sat` < 1), the temporal half of HAVC_stabilizer (`stab=True`), scene detection INSIDE HAVC_colorizer / HAVC_ddeoldify (`sc_threshold` > 0, `sc_min_freq` > 0: the reference-frame
 logic of vs_sc_ddcolor / vs_sc_tweak that hangs off it), the SSIM post-filter INSIDE HAVC_SceneDetect (`sc_tht_ssim` in (0, 1), `sc_min_int` > 1: that refusal is pinned and
-stays; the filter itself is built and runs in HAVC_extract_reference_frames), the plugin scene detectors of HAVC_extract_reference_frames (`sc_algo` 1-3), of HAVC_deepex the exemplar models 1-3 (Deep-Exemplar, DeepRemaster: not built), methods 1-6
+stays; the filter itself is built and runs in HAVC_extract_reference_frames), the plugin scene detectors of HAVC_extract_reference_frames (`sc_algo` 1-3; 1 is built as HAVC_SceneDetectEdges but not routed there yet), of HAVC_deepex the exemplar models 1-3 (Deep-Exemplar, DeepRemaster: not built), methods 1-6
 (reference frames from a directory or a video), `encode_mode` 2 and `sc_framedir` / `only_ref_frames` (they write files), the parts of the DDColor
 pre-tweaks that are VapourSynth filters (`ddtweak`: bright / cont / gamma through vs_tweak, rgb_denoise, retinex), non-RGB24 formats.
 Computed here: the hue adjustment vs_sc_ddcolor applies to every DDColor frame (default "300:360|0.8,0.1") and the luma-constrained
@@ -39,6 +40,10 @@ contract; none of it can be executed where the fixtures are made
     Spline36 on the gray plane -> the library's Spline64 on the RGB clip, at the reference's size; `misc.SCDetect` on the default path (threshold >= 0.10,
     offset 1) -> prev_n = diff(n - 1, n) > threshold, prev_0 = 1, next_n = prev_(n + 1), next_last = 1.  The custom detector (threshold < 0.10 or offset > 1) and
     the black / white filter are the reference's Python, restated and pinned by tests/golden/scdetect.npz.
+  * HAVC_SceneDetectEdges (vsdeoldify_amd/scdetect_edge.py has the details): the gray conversion and resize as above; std.Convolution (Kirsch), akarin.Expr,
+    TCanny(mode=1), std.MaskedMerge and std.PlaneStats -> the integer / float32 sequences of tests/scedges_util.py, which csrc/scedge.hip equals byte for
+    byte; misc.SCDetect(threshold=0.10) -> the rule above on the SAD against the previous frame.  Both selectors are the reference's Python, restated and
+    pinned by tests/golden/scdetect_edges.npz -- the missing comma of its prop list included.
   * the SSIM / histogram post-filter (HAVC_extract_reference_frames; scdetect.py has the details): skimage's structural_similarity -> its published formula
     over exact integer 7 x 7 window sums, float64 quotient; cv2's gray -> (4899 R + 9617 G + 1868 B + 8192) >> 14; cv2.calcHist -> exact counts;
     cv2.normalize + compareHist(HELLINGER) (float32 histograms there) -> OpenCV's published definition in float64; the zimg resize of the RGB clip in
@@ -730,6 +735,33 @@ def HAVC_SceneDetect(clip, sc_threshold=0.10, sc_tht_offset=1, sc_tht_ssim=0.0, 
     return scdetect.scene_detect(ctx, clip, threshold=sc_threshold, frequency=sc_min_freq, sc_tht_filter=sc_tht_ssim, min_length=sc_min_int,
                                  tht_white=sc_tht_white, tht_black=sc_tht_black, frame_norm=sc_normalize, tht_offset=sc_tht_offset,
                                  coeffs=scdetect.LUMA_LIMITED if luma_range == "limited" else scdetect.LUMA_FULL)
+
+
+# ---- HAVC_SceneDetectEdges (vsdeoldify/__init__.py:3227-3258 -> vsslib/vsscdetect_edge.py) ---------------------------------------------------------------
+def HAVC_SceneDetectEdges(clip, sc_threshold=0.035, sc_tht_offset=2, sc_tht_ssim=0.80, sc_min_int=20, sc_mult_tht=15, sc_tht_white=0.70, sc_tht_black=0.10,
+                          sc_debug=False, *, device_index=0, luma_range="limited"):
+    """vsdeoldify/__init__.py:3227-3258: the scene-change frames of a clip by the reference's edge-masked detector, the one it recommends for blended and
+    smooth transitions.  The props come back as a `scdetect_edge.EdgeSceneInfo` (a SceneInfo with sc_reason; sc_ratio is zeros), accepted wherever
+    `scenes=` is.  The per-frame statistics are ONE launch over the small clip (havc_scene_edge_stats, csrc/scedge.hip); with sc_tht_ssim > 0 (the default)
+    the SSIM / histogram filter follows: one havc_scene_hist and one havc_scene_ssim launch over the detector's candidates.  A DeviceImage stays in HBM and
+    only per-frame records and scores come back; the decisions are scdetect_edge.edge_detector / edge_scene_filter, on the host.  sc_threshold == 0 flags
+    nothing (the reference's early return).  sc_debug is accepted and ignored.  luma_range as in HAVC_SceneDetect."""
+    from . import scdetect, scdetect_edge
+    if clip is None or not (is_device(clip) or isinstance(clip, np.ndarray)):
+        raise HAVCError("HAVC_SceneDetectEdges: this is not a clip")
+    if luma_range not in ("limited", "full"):
+        raise HAVCError("HAVC_SceneDetectEdges: luma_range must be 'limited' or 'full'")
+    clip, _ = _as_clip(clip)
+    ctx = None                                                                                   # the early return touches no pixel and needs no context
+    if scdetect_edge.edges_branch(sc_threshold, 0) == "detect":
+        try:
+            scdetect_edge.edges_offset(sc_tht_offset, clip.shape[0])
+        except ValueError as e:
+            raise HAVCError("HAVC_SceneDetectEdges: " + str(e)) from None
+        ctx = clip.ctx if is_device(clip) else get_context(device_index)
+    return scdetect_edge.scene_detect_edges(ctx, clip, threshold=sc_threshold, frequency=0, ssim_threshold=sc_tht_ssim, sc_diff_offset=sc_tht_offset,
+                                            sc_min_int=sc_min_int, sc_mult_tht=sc_mult_tht, tht_white=sc_tht_white, tht_black=sc_tht_black,
+                                            coeffs=scdetect.LUMA_LIMITED if luma_range == "limited" else scdetect.LUMA_FULL)
 
 
 # ---- HAVC_extract_reference_frames / HAVC_export_reference_frames / HAVC_export_list_frames (vsdeoldify/__init__.py:3272-3416 -> vsslib/vsutils.py:147-233) ----
