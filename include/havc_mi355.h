@@ -610,6 +610,56 @@ int havc_retinex_clip(havc_ctx* ctx, const uint8_t* src, uint8_t* dst, const hav
 int havc_retinex_frame_params(int64_t sum_y, int64_t n_pixels, int range_tv, double luma_dark, double luma_bright, int blend, double* out);
 /* the recursive Gaussian's coefficients of one sigma in [0.5, 10000], on the host: out4 = {B, B1, B2, B3} */
 int havc_retinex_coefficients(double sigma, double* out4);
+/* HAVC_tweak (vsdeoldify/__init__.py:1377-1408 -> vs_tweak, vsslib/vsfilters.py:753-850): the clip goes RGB24 -> YUV420P8 -> RGB24 (BT.709, full range) and
+ * hue / saturation / brightness / contrast act on the planes in between.  zimg cannot be executed where the fixtures are made; both conversions are an
+ * UNPINNED stand-in whose definition is tests/tweak_util.py, and the kernels equal it byte for byte.  float32, one rounding per operation, never fused:
+ *   forward  r, g, b = sample / 255;  Y = (KR r + KG g) + KB b, KR = 0.2126, KB = 0.0722, KG = 1 - KR - KB;  Cb = (b - Y) / (2 (1 - KB)), Cr = (r - Y) /
+ *            (2 (1 - KR));  Cb, Cr 2 : 1 in both directions through a separable Mitchell bicubic (b = c = 1/3) stretched by 2: taps 2j - 3 .. 2j + 4 summed
+ *            lowest first, vertical pass first with the centre at 2j + 0.5, then horizontal with the centre at 2j; a tap outside the plane reads the mirrored
+ *            sample (-1 -> 0, n -> n - 1); the weights are normalised to sum 1 in float64;  Y8 = clip(rint(Y 255)), C8 = clip(rint(C 255 + 128)).
+ *   back     Y = y / 255, C = (c - 128) / 255;  chroma 1 : 2 with the same kernel, 4 taps, vertical first (centre (i + 0.5) / 2 - 0.5), then horizontal
+ *            (centre i / 2);  R = Y + 2 (1 - KR) Cr, B = Y + 2 (1 - KB) Cb, G = (Y - (2 (1 - KR) KR / KG) Cr) - (2 (1 - KB) KB / KG) Cb, each times 255;
+ *            error diffusion per plane, rows top to bottom and left to right: e = ((left 7/16 + topright 3/16) + top 5/16) + topleft 1/16 of the errors
+ *            already kept (0 outside the plane), v = clamp(x + e, 0, 255), out = rint(v), the pixel keeps v - out.
+ * In between, vs_tweak's own steps: gamma_lut on every RGB sample read (std.Levels(gamma=), the caller's table), U' = ((U - 128) c + (V - 128) s) + 128 and
+ * V' = ((V - 128) c - (U - 128) s) + 128 clamped to 0..255 and rounded half to even (the two std.Expr; c = hue_cos * sat, s = hue_sin * sat as float32),
+ * luma_lut on every Y sample (std.Lut).  Width and height: even, at most 4096.  Long clips go through in chunks of frames; the Y, U, V planes of a chunk are
+ * the only scratch. */
+typedef struct havc_tweak_params {
+    int width, height, n_frames;
+    int has_gamma, has_hue_sat, has_luma;     /* which of the steps run */
+    int chunk_frames;                         /* frames per forward / back launch pair; 0 = the library's choice (at most 256 MiB of planes) */
+    int reserved;
+    double hue_c, hue_s;
+    uint8_t gamma_lut[256], luma_lut[256];
+} havc_tweak_params;
+/* src, dst: host or device pointers like every filter here (dst may be src).  Device operands: the call only enqueues. */
+int havc_tweak_clip(havc_ctx* ctx, const uint8_t* src, uint8_t* dst, const havc_tweak_params* params);
+/* the two halves on their own, full range BT.709 as above: src / dst [n_frames][height][width][3], y [n_frames][height][width], u and v
+ * [n_frames][height / 2][width / 2]; every pointer host or device on its own.  An odd or oversized frame: HAVC_E_INVALID, nothing runs. */
+int havc_rgb_to_yuv420(havc_ctx* ctx, const uint8_t* src, uint8_t* y, uint8_t* u, uint8_t* v, int width, int height, int n_frames);
+int havc_yuv420_to_rgb(havc_ctx* ctx, const uint8_t* y, const uint8_t* u, const uint8_t* v, uint8_t* dst, int width, int height, int n_frames);
+/* the chroma filters of the calls above, on the host (no context, no GPU): out32 = the 8 weights of the vertical 2 : 1 pass, the 8 of the horizontal one,
+ * 2 x 4 of the vertical 1 : 2 pass (even output row, odd), 2 x 4 of the horizontal one */
+int havc_tweak_weights(float* out32);
+/* HAVC_adjust_rgb (vsdeoldify/__init__.py:1342-1374 -> vs_rgb_normalize, vsslib/vsfilters.py:1013-1038, and adjust_rgb, havc_utils.py:664-749) on a clip: every
+ * stage is a function of the sample's own value and the frame's three channel means, so the call is three launches -- the channel sums (normalize != 0),
+ * 3 x 256 bytes per frame composed on the device in float64, one pass that applies them -- and nothing is read back.
+ *   normalize 1: sample -> clip(rint(float32(sample) * float32(gain))) with the grey-world gains of the frame (from PlaneStatsAverage = sum / (n_pixels 255),
+ *   NOT rounded);  normalize 2: std.Merge(sample, normalised, strength) = a + (((b - a) * int(strength * 32768 + 0.5) + 16384) >> 15);
+ *   then clip(rint(float32(sample) * gain[c] + bias[c])) (std.Expr "x r * rb +": product, then sum), then gamma_lut[c] (std.Levels(gamma=), the caller's
+ *   table; identity: none). */
+typedef struct havc_adjust_params {
+    int width, height, n_frames;  /* at most 2^30 pixels per frame */
+    int normalize;                /* 0..2 */
+    double strength;              /* normalize 2: in (0, 1) */
+    float gain[3], bias[3];
+    uint8_t gamma_lut[3][256];
+} havc_adjust_params;
+/* src, dst: host or device pointers; dst must not be src.  Device operands: the call only enqueues. */
+int havc_adjust_rgb_clip(havc_ctx* ctx, const uint8_t* src, uint8_t* dst, const havc_adjust_params* params);
+/* the gains of normalize != 0 from a frame's three channel sums, on the host (no context, no GPU): out3 in float64 */
+int havc_adjust_frame_params(const int64_t* chan_sums, int64_t n_pixels, double* out3);
 /* the per-pixel half of luma_adjusted_levels (vsslib/imfilters.py:335-372): cv2 RGB->YUV, Y' = lut[Y], YUV->RGB.  The caller
  * derives the 256-entry table from havc_image_luma exactly like the reference (vsdeoldify_amd/imfilters.py). */
 int havc_luma_lut(havc_ctx* ctx, const uint8_t* img, const uint8_t* lut256, uint8_t* out, int width, int height);

@@ -101,6 +101,19 @@ class RetinexParams(C.Structure):
                 ("blend", C.c_int), ("chunk_frames", C.c_int), ("reserved", C.c_int)]
 
 
+class TweakParams(C.Structure):
+    """`havc_tweak_params` (include/havc_mi355.h): clip size, which of vs_tweak's steps run, the hue / sat products and the two tables of havc_tweak_clip"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int), ("has_gamma", C.c_int), ("has_hue_sat", C.c_int), ("has_luma", C.c_int),
+                ("chunk_frames", C.c_int), ("reserved", C.c_int), ("hue_c", C.c_double), ("hue_s", C.c_double), ("gamma_lut", C.c_uint8 * 256),
+                ("luma_lut", C.c_uint8 * 256)]
+
+
+class AdjustParams(C.Structure):
+    """`havc_adjust_params` (include/havc_mi355.h): clip size, normalisation, the affine step and the per-plane gamma tables of havc_adjust_rgb_clip"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int), ("normalize", C.c_int), ("strength", C.c_double), ("gain", C.c_float * 3),
+                ("bias", C.c_float * 3), ("gamma_lut", (C.c_uint8 * 256) * 3)]
+
+
 class RecoverParams(C.Structure):
     """`havc_recover_params` (include/havc_mi355.h): clip size, first frame number and the arguments of ChromaRetentionMerge's selectors (havc_recover_color_clip)"""
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int), ("first_frame", C.c_int), ("sat", C.c_double), ("tht", C.c_int),
@@ -191,6 +204,12 @@ SYMBOLS = [
     ("havc_retinex_clip", _I, [_P, _P, _P, _P, _P]),
     ("havc_retinex_frame_params", _I, [C.c_int64, C.c_int64, _I, _D, _D, _I, _P]),
     ("havc_retinex_coefficients", _I, [_D, _P]),
+    ("havc_tweak_clip", _I, [_P, _P, _P, _P]),
+    ("havc_rgb_to_yuv420", _I, [_P, _P, _P, _P, _P, _I, _I, _I]),
+    ("havc_yuv420_to_rgb", _I, [_P, _P, _P, _P, _P, _I, _I, _I]),
+    ("havc_tweak_weights", _I, [_P]),
+    ("havc_adjust_rgb_clip", _I, [_P, _P, _P, _P]),
+    ("havc_adjust_frame_params", _I, [_P, C.c_int64, _P]),
     ("havc_luma_lut", _I, [_P, _P, _P, _P, _I, _I]),
     ("havc_restore_color_gradient", _I, [_P, _P, _P, _P, _I, _I, _D, _I, _D, _D, _I, _I]),
     ("havc_recover_color_clip", _I, [_P, _P, _P, _P, _P]),

@@ -360,4 +360,17 @@ int launch_equalize(const uint8_t* src, uint8_t* dst, void* ws, EqArgs a, hipStr
     return (int)hipGetLastError();
 }
 
+// the channel sums alone (HAVC_adjust_rgb's normalisation): identity table, rec[f].chan only
+int launch_equalize_chan_sums(const uint8_t* src, void* rec, int n, int h, int w, hipStream_t s) {
+    const int64_t npix = (int64_t)h * w;
+    if (n <= 0 || h <= 0 || w <= 0 || npix > ((int64_t)1 << 30)) return (int)hipErrorInvalidValue;
+    EqArgs a{};
+    a.n = n; a.h = h; a.w = w;
+    for (int v = 0; v < 256; ++v) a.lut_in[v] = (uint8_t)v;
+    a.blocks_per_frame = eq_blocks_per_frame(npix);
+    if ((int64_t)n * a.blocks_per_frame > 0x7FFFFFFFll) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(eq_chan_sum_kernel, dim3((unsigned)((int64_t)n * a.blocks_per_frame)), dim3(EQ_THREADS), 0, s, src, (EqFrameRec*)rec, a);
+    return (int)hipGetLastError();
+}
+
 void preload_equalize() { hipFuncAttributes a; (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(eq_lut_kernel)); (void)hipGetLastError(); }

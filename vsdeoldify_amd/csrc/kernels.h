@@ -250,6 +250,33 @@ size_t retinex_record_bytes(int n);                  // the per-frame records an
 // planes: n * ns float64 planes of h * w; rec: retinex_record_bytes(n) bytes, zero-filled on the same stream in front of the call; tap_g / tap_p (both or
 // neither, device memory): the n * ns Gaussian planes and the n MSR product planes, for the tests
 int launch_retinex(const uint8_t* src, uint8_t* dst, double* planes, void* rec, double* tap_g, double* tap_p, RetArgs a, hipStream_t s);
+// the channel sums of every frame alone (eq_chan_sum_kernel with an identity table): rec = n zero-filled EqFrameRec, only .chan is written
+int launch_equalize_chan_sums(const uint8_t* src, void* rec, int n, int h, int w, hipStream_t s);
+// tweak.hip: HAVC_tweak's RGB24 <-> YUV420P8 round trip (BT.709 full range, Mitchell bicubic chroma, error diffusion on the way back: the stand-in of
+// tests/tweak_util.py) and HAVC_adjust_rgb as per-frame tables, on a clip [n][h][w][3] (vsslib/vsfilters.py:753-850, havc_utils.py:664-749)
+#define TW_MAX_SIDE 4096          // width and height: the back kernel keeps one error row per channel in LDS
+struct TweakWeights { float down_v[8], down_h[8], up_v[2][4], up_h[2][4]; };      // the chroma filters (tweak_ops.h: tw_all_weights), set by the launchers
+struct TweakFwdArgs {
+    int n, h, w;                  // frames of the chunk (at most 65535), frame size (even, at most TW_MAX_SIDE)
+    int has_gamma, has_hue_sat, has_luma;
+    float hue_c, hue_s;           // hue_cos * sat, hue_sin * sat as std.Expr's float32 constants
+    uint8_t gamma_lut[256];       // applied to every RGB sample read
+    uint8_t luma_lut[256];        // applied to every Y sample written
+    TweakWeights wt;
+};
+struct TweakBackArgs { int n, h, w; TweakWeights wt; };
+int launch_tweak_forward(const uint8_t* src, uint8_t* y, uint8_t* u, uint8_t* v, TweakFwdArgs a, hipStream_t s);
+int launch_tweak_back(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint8_t* dst, TweakBackArgs a, hipStream_t s);
+struct AdjustArgs {
+    int n, h, w;
+    int mode;                     // 0: no normalisation, 1: vs_rgb_normalize, 2: std.Merge(clip, normalised, strength)
+    int w15;                      // mode 2: int(strength * 32768 + 0.5)
+    float gain[3], bias[3];       // "x r * rb +"
+    uint8_t gamma_lut[3][256];    // std.Levels(gamma=) per plane (identity: none)
+    int blocks_per_frame;         // set by launch_adjust_rgb
+};
+// rec: n zero-filled EqFrameRec (used with mode != 0); tables: n * 768 bytes; both device memory
+int launch_adjust_rgb(const uint8_t* src, uint8_t* dst, void* rec, uint8_t* tables, AdjustArgs a, hipStream_t s);
 // separable polyphase resample of interleaved u8 RGB (tap tables from the host; Spline64 = harness stand-in
 // for zimg resize.Spline64).  orig != null fuses chroma_post_process (luma of orig, chroma of the resampled).
 int launch_resize_passes(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, int n_frames, float* tmp,
@@ -301,6 +328,7 @@ void preload_scfilter();
 void preload_scedge();
 void preload_equalize();
 void preload_retinex();
+void preload_tweak_clip();
 void preload_ddcolor();
 void preload_colormnet();
 void preload_colormnet_net();

@@ -5,6 +5,7 @@
 #include "scedge_ops.h"
 #include "equalize_ops.h"
 #include "retinex_ops.h"
+#include "tweak_ops.h"
 
 extern "C" {
 
@@ -508,6 +509,175 @@ int havc_retinex_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const havc_
         }
     }
     if (tap && !is_device_ptr(tap)) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return stage_out(c, dst, d_dst, cb, host);
+}
+
+// ---- HAVC_tweak: RGB24 -> YUV420P8 -> RGB24 with vs_tweak's steps in between, and HAVC_adjust_rgb as per-frame tables (tweak.hip) ----
+static_assert(sizeof(havc_tweak_params) == 560, "havc_tweak_params layout");
+static_assert(sizeof(havc_adjust_params) == 816, "havc_adjust_params layout");
+
+int havc_tweak_weights(float* out32) {
+    if (!out32) return HAVC_E_INVALID;
+    TweakWeights t;
+    tw_all_weights(t);
+    memcpy(out32, &t, sizeof(t));
+    return HAVC_OK;
+}
+
+static int tweak_size_check(havc_ctx* c, const char* what, int width, int height, int n_frames) {
+    if (width < 2 || height < 2 || n_frames <= 0 || (width & 1) || (height & 1) || width > TW_MAX_SIDE || height > TW_MAX_SIDE)
+        return fail(c, HAVC_E_INVALID, std::string(what) + ": bad clip size (YUV420 needs an even width and height; at most 4096 x 4096)");
+    return HAVC_OK;
+}
+
+// Frames per forward / back launch pair: the planes of a chunk stay under 256 MiB, and a launch takes at most 65535 frames (grid z).
+static int tweak_chunk_frames(int width, int height, int n_frames, int want) {
+    const int64_t per_frame = (int64_t)width * height * 3 / 2;
+    const int64_t cap = std::max<int64_t>(1, ((int64_t)256 << 20) / per_frame);
+    int64_t k = want > 0 ? want : cap;
+    k = std::min<int64_t>(std::min<int64_t>(k, 65535), n_frames);
+    return (int)k;
+}
+
+// a plane set that is partly in host memory: device planes are used in place, host planes get room in SCR_TWEAK_YUV
+struct TweakPlanes { uint8_t* d[3]; bool host[3]; size_t bytes[3]; };
+static int tweak_stage_planes(havc_ctx* c, uint8_t* const p[3], int width, int height, int n_frames, bool upload, TweakPlanes* out) {
+    const size_t pb = (size_t)n_frames * width * height;
+    out->bytes[0] = pb; out->bytes[1] = out->bytes[2] = pb / 4;
+    size_t need = 0;
+    for (int k = 0; k < 3; ++k) { out->host[k] = !is_device_ptr(p[k]); if (out->host[k]) need += out->bytes[k]; }
+    int rc;
+    if (need && (rc = ensure_scratch(c, SCR_TWEAK_YUV, need))) return rc;
+    size_t off = 0;
+    for (int k = 0; k < 3; ++k) {
+        if (!out->host[k]) { out->d[k] = p[k]; continue; }
+        out->d[k] = (uint8_t*)c->scratch[SCR_TWEAK_YUV] + off;
+        off += out->bytes[k];
+        if (upload) HIP_TRY(c, hipMemcpyAsync(out->d[k], p[k], out->bytes[k], hipMemcpyHostToDevice, c->stream));
+    }
+    return HAVC_OK;
+}
+
+int havc_rgb_to_yuv420(havc_ctx* c, const uint8_t* src, uint8_t* y, uint8_t* u, uint8_t* v, int width, int height, int n_frames) {
+    if (!c || !src || !y || !u || !v) return fail(c, HAVC_E_INVALID, "rgb_to_yuv420: bad args");
+    int rc = tweak_size_check(c, "rgb_to_yuv420", width, height, n_frames);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    const size_t pb = (size_t)width * height, qb = pb / 4;
+    const uint8_t* d_src;
+    uint8_t* const planes[3] = {y, u, v};
+    TweakPlanes tp;
+    if ((rc = stage_in(c, SCR_IN, src, (size_t)n_frames * pb * 3, &d_src)) || (rc = tweak_stage_planes(c, planes, width, height, n_frames, false, &tp))) return rc;
+    TweakFwdArgs a{};
+    a.h = height; a.w = width;
+    const int chunk = tweak_chunk_frames(width, height, n_frames, 0);
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        a.n = std::min(chunk, n_frames - f0);
+        const int e = launch_tweak_forward(d_src + (size_t)f0 * pb * 3, tp.d[0] + (size_t)f0 * pb, tp.d[1] + (size_t)f0 * qb, tp.d[2] + (size_t)f0 * qb, a, c->stream);
+        c->stats.launches++;
+        if (e) return hip_fail(c, (hipError_t)e, "rgb_to_yuv420");
+    }
+    bool any_host = false;
+    for (int k = 0; k < 3; ++k)
+        if (tp.host[k]) { any_host = true; HIP_TRY(c, hipMemcpyAsync(planes[k], tp.d[k], tp.bytes[k], hipMemcpyDeviceToHost, c->stream)); }
+    if (any_host) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HAVC_OK;
+}
+
+int havc_yuv420_to_rgb(havc_ctx* c, const uint8_t* y, const uint8_t* u, const uint8_t* v, uint8_t* dst, int width, int height, int n_frames) {
+    if (!c || !y || !u || !v || !dst) return fail(c, HAVC_E_INVALID, "yuv420_to_rgb: bad args");
+    int rc = tweak_size_check(c, "yuv420_to_rgb", width, height, n_frames);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    const size_t pb = (size_t)width * height, qb = pb / 4, cb = (size_t)n_frames * pb * 3;
+    uint8_t* const planes[3] = {const_cast<uint8_t*>(y), const_cast<uint8_t*>(u), const_cast<uint8_t*>(v)};
+    TweakPlanes tp;
+    uint8_t* d_dst;
+    bool host;
+    if ((rc = tweak_stage_planes(c, planes, width, height, n_frames, true, &tp)) || (rc = stage_out_ptr(c, SCR_OUT, dst, cb, &d_dst, &host))) return rc;
+    TweakBackArgs a{};
+    a.h = height; a.w = width;
+    const int chunk = tweak_chunk_frames(width, height, n_frames, 0);
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        a.n = std::min(chunk, n_frames - f0);
+        const int e = launch_tweak_back(tp.d[0] + (size_t)f0 * pb, tp.d[1] + (size_t)f0 * qb, tp.d[2] + (size_t)f0 * qb, d_dst + (size_t)f0 * pb * 3, a, c->stream);
+        c->stats.launches++;
+        if (e) return hip_fail(c, (hipError_t)e, "yuv420_to_rgb");
+    }
+    return stage_out(c, dst, d_dst, cb, host);
+}
+
+int havc_tweak_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const havc_tweak_params* p) {
+    if (!c || !src || !dst || !p) return fail(c, HAVC_E_INVALID, "tweak_clip: bad args");
+    int rc = tweak_size_check(c, "tweak_clip", p->width, p->height, p->n_frames);
+    if (rc) return rc;
+    if (p->chunk_frames < 0) return fail(c, HAVC_E_INVALID, "tweak_clip: chunk_frames must be >= 0");
+    if (p->has_hue_sat && !(std::isfinite(p->hue_c) && std::isfinite(p->hue_s))) return fail(c, HAVC_E_INVALID, "tweak_clip: hue_c / hue_s must be finite");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    TweakFwdArgs fa{};
+    fa.h = p->height; fa.w = p->width;
+    fa.has_gamma = p->has_gamma != 0; fa.has_hue_sat = p->has_hue_sat != 0; fa.has_luma = p->has_luma != 0;
+    fa.hue_c = (float)p->hue_c; fa.hue_s = (float)p->hue_s;
+    memcpy(fa.gamma_lut, p->gamma_lut, 256);
+    memcpy(fa.luma_lut, p->luma_lut, 256);
+    TweakBackArgs ba{};
+    ba.h = p->height; ba.w = p->width;
+    const int chunk = tweak_chunk_frames(p->width, p->height, p->n_frames, p->chunk_frames);
+    const size_t pb = (size_t)p->width * p->height, qb = pb / 4, fb = pb * 3, cb = (size_t)p->n_frames * fb;
+    const uint8_t* d_src;
+    uint8_t* d_dst;
+    bool host;
+    if ((rc = stage_in(c, SCR_IN, src, cb, &d_src)) || (rc = stage_out_ptr(c, SCR_OUT, dst, cb, &d_dst, &host)) ||
+        (rc = ensure_scratch(c, SCR_TWEAK_YUV, (size_t)chunk * (pb + 2 * qb)))) return rc;
+    uint8_t* d_y = (uint8_t*)c->scratch[SCR_TWEAK_YUV];
+    uint8_t* d_u = d_y + (size_t)chunk * pb;
+    uint8_t* d_v = d_u + (size_t)chunk * qb;
+    for (int f0 = 0; f0 < p->n_frames; f0 += chunk) {
+        fa.n = ba.n = std::min(chunk, p->n_frames - f0);
+        int e = launch_tweak_forward(d_src + (size_t)f0 * fb, d_y, d_u, d_v, fa, c->stream);
+        if (!e) e = launch_tweak_back(d_y, d_u, d_v, d_dst + (size_t)f0 * fb, ba, c->stream);
+        c->stats.launches += 2;
+        if (e) return hip_fail(c, (hipError_t)e, "tweak_clip");
+    }
+    return stage_out(c, dst, d_dst, cb, host);
+}
+
+int havc_adjust_frame_params(const int64_t* chan_sums, int64_t n_pixels, double* out3) {
+    if (!chan_sums || !out3 || n_pixels <= 0 || chan_sums[0] < 0 || chan_sums[1] < 0 || chan_sums[2] < 0) return HAVC_E_INVALID;
+    const unsigned long long ch[3] = {(unsigned long long)chan_sums[0], (unsigned long long)chan_sums[1], (unsigned long long)chan_sums[2]};
+    tw_normalize_gains(ch, n_pixels, out3);
+    return HAVC_OK;
+}
+
+int havc_adjust_rgb_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const havc_adjust_params* p) {
+    if (!c || !src || !dst || !p) return fail(c, HAVC_E_INVALID, "adjust_rgb_clip: bad args");
+    if (src == dst) return fail(c, HAVC_E_INVALID, "adjust_rgb_clip: dst must not be src");
+    if (p->n_frames <= 0 || p->width <= 0 || p->height <= 0 || (int64_t)p->width * p->height > ((int64_t)1 << 30))
+        return fail(c, HAVC_E_INVALID, "adjust_rgb_clip: bad clip size (at most 2^30 pixels per frame)");
+    if (p->normalize < 0 || p->normalize > 2) return fail(c, HAVC_E_INVALID, "adjust_rgb_clip: normalize must be 0..2");
+    if (p->normalize == 2 && !(p->strength > 0.0 && p->strength < 1.0)) return fail(c, HAVC_E_INVALID, "adjust_rgb_clip: strength must be in (0, 1) with normalize 2");
+    for (int k = 0; k < 3; ++k)
+        if (!(std::isfinite(p->gain[k]) && std::isfinite(p->bias[k]))) return fail(c, HAVC_E_INVALID, "adjust_rgb_clip: gain / bias must be finite");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    AdjustArgs a{};
+    a.n = p->n_frames; a.h = p->height; a.w = p->width; a.mode = p->normalize;
+    a.w15 = p->normalize == 2 ? eq_w15(p->strength) : 0;
+    for (int k = 0; k < 3; ++k) { a.gain[k] = p->gain[k]; a.bias[k] = p->bias[k]; }
+    memcpy(a.gamma_lut, p->gamma_lut, sizeof(a.gamma_lut));
+    const size_t cb = (size_t)a.n * a.h * a.w * 3, rb = (size_t)a.n * sizeof(EqFrameRec), tb = (size_t)a.n * 3 * 256;
+    int rc;
+    const uint8_t* d_src;
+    uint8_t* d_dst;
+    bool host;
+    if ((rc = stage_in(c, SCR_IN, src, cb, &d_src)) || (rc = stage_out_ptr(c, SCR_OUT, dst, cb, &d_dst, &host)) || (rc = ensure_scratch(c, SCR_ADJUST_TABLES, rb + tb))) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->scratch[SCR_ADJUST_TABLES], 0, rb, c->stream));
+    const int e = launch_adjust_rgb(d_src, d_dst, c->scratch[SCR_ADJUST_TABLES], (uint8_t*)c->scratch[SCR_ADJUST_TABLES] + rb, a, c->stream);
+    c->stats.launches += a.mode ? 3 : 2;
+    if (e) return hip_fail(c, (hipError_t)e, "adjust_rgb_clip");
     return stage_out(c, dst, d_dst, cb, host);
 }
 

@@ -82,8 +82,11 @@ enum ScratchSlot {
     SCR_PLANES_OUT = SCR_IN5,          //   havc_ddcolor_frame_planar_f: the float / half planes on their way out
     SCR_SMALL = 6,                     // small results and tables: luma sums, a 256-byte LUT, scene records, the equalisation workspace, a usage vector,
                                        // the Retinex records and histograms of a chunk
+    SCR_ADJUST_TABLES = SCR_SMALL,     //   havc_adjust_rgb_clip: the channel sums of every frame, then its three 256-byte tables
     SCR_RESIZE_ROWS = 7,               // fp32 rows between the two passes of the Spline64 resize
     SCR_RETINEX_PLANES = SCR_RESIZE_ROWS,   //   havc_retinex_clip: the float64 Gaussian planes of a CHUNK of frames (n_sigmas per frame; bounded by the chunk)
+    SCR_TWEAK_YUV = SCR_RESIZE_ROWS,        //   havc_tweak_clip: the Y, then U, then V planes of a CHUNK of frames between the two conversions; the two halves on
+                                            //   their own (havc_rgb_to_yuv420 / havc_yuv420_to_rgb): host planes on their way in or out
     // 8-11: the pipelined host clip (havc_colorize_clip_host), double-buffered by batch parity; the ONE-SHOT ColorMNet reads reuse them
     SCR_CLIP_SRC = 8,                  // 8, 9: source batches, SCR_CLIP_SRC + (batch & 1)
     SCR_SIM = SCR_CLIP_SRC,            //   one-shot read: similarity map [B][N][HW]; havc_local_attention: the attention map

@@ -13,6 +13,9 @@
     HAVC_recover_clip_color vsdeoldify/__init__.py:2956-2992   (ChromaRetentionMerge on a clip: gradient and binary mask, chroma_resize through the library's Spline64)
     HAVC_restore_video vsdeoldify/__init__.py:1959-2127   (colour transfer from a reference video: ex_model 0 = ColorMNet, 2 = DeepRemaster's clip mode; methods 5, 6)
     HAVC_retinex     vsdeoldify/__init__.py:1073-1101     (multi-scale Retinex, MSRCP, with the luma gate and blend of vs_retinex_fast; float64 Gaussians; retinex.py)
+    HAVC_tweak       vsdeoldify/__init__.py:1377-1408     (hue, saturation, brightness, contrast, gamma through a YUV420P8 round trip; tweak.py)
+    HAVC_adjust_rgb  vsdeoldify/__init__.py:1342-1374     (grey-world normalisation, per-channel gain, bias and gamma as per-frame tables; tweak.py)
+    HAVC_rgb_denoise vsdeoldify/__init__.py:924-944       (rgb_balance + CLAHE on luma between the TV-range conversions: the equalize.py path)
 
 Same names, argument lists, defaults, parameter normalisation, frame-size rule, model routing, combine dispatch
 (vsslib/mcomb.py:125-192) and error texts; a "clip" is a uint8 array [n, h, w, 3] (or one frame [h, w, 3], or a
@@ -59,6 +62,12 @@ contract; none of it can be executed where the fixtures are made
     with the Young - van Vliet recursive Gaussian, float64, restated in tests/retinex_util.py -- the plugin cannot be executed where the fixtures are made.
     The gate, the f_luma roundings, the blend weight, Pillow's blend and the arguments handed to the plugin are the reference's Python, restated and pinned
     by tests/golden/retinex.npz.  `chroma_resize=True` is refused; method 5 of HAVC_bw_tune / HAVC_auto_levels is not routed here yet and stays refused.
+  * HAVC_tweak / HAVC_adjust_rgb / HAVC_rgb_denoise (vsdeoldify_amd/tweak.py has the details): zimg's `resize.Bicubic` RGB24 -> YUV420P8 -> RGB24 (BT.709,
+    full range; Mitchell bicubic chroma resampling, `dither_type="error_diffusion"` on the way back), `std.Levels(gamma=)`, `std.Expr`, `std.Lut` -> the
+    float32 sequences of tests/tweak_util.py, which csrc/tweak.hip equals byte for byte; none of it can be executed where the fixtures are made.  What
+    vs_tweak, adjust_rgb, vs_rgb_normalize and rgb_denoise hand to those filters is the reference's Python, restated and pinned by tests/golden/tweak.npz.
+    The `vs_tweak` refusals INSIDE the other entry points (HAVC_colorizer's sat / hue, HAVC_DeepRemaster / HAVC_restore_video render_vivid, ddtweak,
+    HAVC_stabilizer(stab=True)) stay exactly as they are: existing tests pin them, and routing them to the new code is a separate decision.
 HAVC_clip_slice pads where the reference's std.CropAbs would leave the padded clip by one pixel (an odd width / height with overlap 0: VapourSynth
 raises there); every other geometry CropAbs refuses -- an overlap >= the base tile, a negative overlap -- is refused with HAVCError.
 
@@ -1147,6 +1156,60 @@ def HAVC_retinex(clip, luma_dark=0.20, luma_bright=0.80, sigmas=(25, 80, 250), r
     if single:
         return out.reshaped(out.shape[1:]) if is_device(out) else out[0]
     return out
+
+
+# ---- HAVC_tweak / HAVC_adjust_rgb / HAVC_rgb_denoise (vsdeoldify/__init__.py:1377-1408, 1342-1374, 924-944) ----------------------------------------------
+def _is_clip(clip):
+    return clip is not None and (is_device(clip) or isinstance(clip, np.ndarray))
+
+
+def HAVC_tweak(clip=None, hue=0, sat=1, bright=0, cont=1, gamma=1, *, device_index=0):
+    """vsdeoldify/__init__.py:1377-1408 -> vs_tweak: hue (degrees), saturation, brightness (-1 < bright < 1 is scaled by 255), contrast and gamma of an RGB24
+    clip, through YUV420P8 (BT.709, full range) and back with error diffusion.  The two conversions are a stand-in for zimg with one written definition
+    (tweak.py says what is pinned and what is not); the kernels equal it byte for byte.  The neutral call returns the clip.  One havc_tweak_clip call: two
+    launches per chunk of frames.  A frame or a clip; ndarray in -> ndarray out; DeviceImage in -> DeviceImage out (nothing leaves HBM, the call only
+    enqueues).  An odd width or height (VapourSynth refuses YUV420 there) and gamma <= 0 are refused.  The vs_tweak refusals inside HAVC_colorizer,
+    HAVC_DeepRemaster, HAVC_restore_video, ddtweak and HAVC_stabilizer(stab=True) stay: routing them here is a separate decision."""
+    from . import tweak
+    if not _is_clip(clip):
+        raise HAVCError("HAVC_tweak: this is not a clip")
+    tweak.check_clip(tuple(clip.shape), clip.dtype if isinstance(clip, np.ndarray) else np.uint8, "HAVC_tweak", True)
+    if not gamma > 0:
+        raise HAVCError(f"HAVC_tweak: gamma = {gamma}: std.Levels needs gamma > 0")
+    plan = tweak.tweak_plan(hue, sat, bright, cont, gamma)
+    if plan is None:                                                                              # vsfilters.py:781-782
+        return clip
+    ctx = clip.ctx if is_device(clip) else get_context(device_index)
+    return tweak.tweak_np(ctx, clip, plan)
+
+
+def HAVC_adjust_rgb(clip=None, strength=0.0, factor=(1.0, 1.0, 1.0), bias=(0, 0, 0), gamma=(1.0, 1.0, 1.0), *, device_index=0, color_range=None):
+    """vsdeoldify/__init__.py:1342-1374: grey-world normalisation of every frame (vs_rgb_normalize; strength 1 = all of it, 0 < strength < 1 = std.Merge by
+    strength, anything else = none), then per channel x * factor + bias and gamma (adjust_rgb).  Every stage is a function of the sample and the frame's
+    channel means: the library composes 3 x 256 bytes per frame on the device and applies them in one pass (three launches, nothing read back).
+    color_range: the reference asks the clip's range prop and an array has none -- None and "limited" take its limited branch, which is also what it does
+    to a clip without the prop (a bias is scaled by 256 / 235 and must lie in [-235, 235]); "full": 256 / 255 and [-255, 255].  A frame or a clip; ndarray
+    in -> ndarray out; DeviceImage in -> DeviceImage out (the call only enqueues)."""
+    from . import tweak
+    if not _is_clip(clip):
+        raise HAVCError("HAVC_adjust_rgb: this is not a clip")
+    tweak.check_clip(tuple(clip.shape), clip.dtype if isinstance(clip, np.ndarray) else np.uint8, "HAVC_adjust_rgb", False)
+    plan = tweak.adjust_plan(factor, bias, gamma, color_range)
+    ctx = clip.ctx if is_device(clip) else get_context(device_index)
+    return tweak.adjust_rgb_np(ctx, clip, strength, plan)
+
+
+def HAVC_rgb_denoise(clip=None, denoise_levels=(0.4, 0.3), rgb_factors=(0.95, 1.05, 1.01), *, device_index=0):
+    """vsdeoldify/__init__.py:924-944 -> rgb_denoise (havc_utils.py:752-773): colour post-process for DDColor / Zhang clips -- between the TV-range
+    conversions, rgb_balance(strength = denoise_levels[0], rgb_factors) and rgb_equalizer(method 0 = CLAHE on luma, strength = denoise_levels[1],
+    luma_blend off, range_tv on).  One havc_equalize_clip call, three launches; frames of at least 8 x 8.  ndarray in -> ndarray out; DeviceImage in ->
+    DeviceImage out (the call only enqueues)."""
+    if not _is_clip(clip):
+        raise HAVCError("HAVC_rgb_denoise: this is not a clip")
+    from . import tweak
+    tweak.check_clip(tuple(clip.shape), clip.dtype if isinstance(clip, np.ndarray) else np.uint8, "HAVC_rgb_denoise", False)
+    return _equalize_clip(clip, device_index, method=0, strength=denoise_levels[1], luma_blend=False, range_tv=True, range_tv_tables=True,
+                          balance=(denoise_levels[0], [rgb_factors[0], rgb_factors[1], rgb_factors[2]]))
 
 
 # ---- HAVC_DeepRemaster (vsdeoldify/__init__.py:2689-2735 -> remaster/__init__.py:203-307 vs_remaster_colorize) ----------------------------------------
