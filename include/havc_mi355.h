@@ -642,6 +642,55 @@ int havc_yuv420_to_rgb(havc_ctx* ctx, const uint8_t* y, const uint8_t* u, const 
 /* the chroma filters of the calls above, on the host (no context, no GPU): out32 = the 8 weights of the vertical 2 : 1 pass, the 8 of the horizontal one,
  * 2 x 4 of the vertical 1 : 2 pass (even output row, odd), 2 x 4 of the horizontal one */
 int havc_tweak_weights(float* out32);
+/* HAVC_stabilizer(stab=True) (vsdeoldify/__init__.py:2862-2866): vs_chroma_stabilizer_ex (vsslib/vsfilters.py:38-63, 84-157, 216-356) with hue_adjust 'none'
+ * and algo 0, then (flicker != 0) vs_reduce_flicker, on a whole clip [n_frames][height][width][3].  VapourSynth, zimg and the ReduceFlicker plugin cannot be
+ * executed where the fixtures are made: everything native is an UNPINNED stand-in whose definition is tests/stab_util.py (on top of tests/tweak_util.py), and
+ * the kernels equal it byte for byte.  The stand-ins:
+ *   conversions    RGB24 <-> YUV420P8 as havc_tweak_clip above; the way back with error diffusion, the way forward without (8 bit in, 8 bit out).
+ *   AverageFrames  8 bit, the caller's integer weights (n_weights = N, odd, 3..15), scale 100, planes U and V:  out = clamp((sum w_i s_i + 50) / 100
+ *                  rounded down, 0, 255); Y is the MIDDLE input's.  Temporal form: slot k of frame n is frame n + k - (N - 1) / 2 clamped to the clip; with
+ *                  scene changes, walking back from the centre, at the first slot whose frame has scene_prev != 0 every earlier slot becomes that frame,
+ *                  and walking forward likewise with scene_next (scene_prev / scene_next: host arrays of n_frames bytes, NULL = none).
+ *   ReduceFlicker  (strength 2, aggressive 0) RESTATED FROM MEMORY of the plugin's scalar code: per sample of each RGB plane, frames n < 2 and n > last - 2 pass
+ *                  through; otherwise with p2, p1, c, n1, n2 the sample in frames n - 2 .. n + 2:  d = min(|c - p2|, |c - n2|), avg = (p1 + 2 c + n1 + 2)
+ *                  >> 2, ul = max(min(p1, n1) - d, c), ll = min(max(p1, n1) + d, c), out = min(max(avg, ll), ul).
+ * tht == 0 (vs_clip_color_stabilizer): forward, the temporal average of U and V with the scene walk, back.
+ * tht > 0 (_average_clips_ex; the scene arrays are not used): for every d in -(N - 1) / 2 .. -1, 1 .. (N - 1) / 2 the shifted clip (vs_get_clip_frame) has
+ * frame n = back(Y_n, U_m, V_m), m = clamp(n + d, 0, last), error diffusion applied.  Frame n of it with first_frame + n < 15 stays as it is
+ * (vs_sc_recover_clip_color's `if n < 15`: the one thing the host decides).  Otherwise, from two integer sums over that frame taken with 64-bit integer
+ * atomics -- cv2's Y, and the count of pixels whose cv2 HSV saturation is < tht -- the device decides:  f_luma = round(sum / n_pixels / 255, 6) outside
+ * 0.22 .. 0.78 makes the weight min(weight, -0.8);  scenechange = ((255 count) / n_pixels) / 255 in float64 (np.mean of the 0 / 255 mask, / 255); with
+ * 0 < tht_scen < 1 and scenechange > tht_scen the frame stays as it is (restore_color's gate, vsslib/restcolor.py:55-61); else every pixel is
+ * restore_color's binary path exactly as havc_recover_color_clip (binary_mask != 0) documents it, colours from frame n of the clip.  Each restored clip goes
+ * forward again, and U / V are the list-form average over [restored_-(N-1)/2 .. restored_-1, the clip, restored_1 ..] with Y of the clip; then back.
+ * Neither the Y planes nor the float planes of the restored clips reach memory: restore_color runs inside the forward conversion's load.
+ * Long clips go through in chunks: chunk_frames output frames (0: the library's choice -- the shifted clips of a chunk stay under 512 MiB, a chunk's source
+ * window under 1024 frames) with a halo of (N - 1) / 2 + 2 source frames on either side (2 of them for the flicker window).  Scratch is bounded by the chunk:
+ * with S = chunk_frames + 4 and A = S + N - 1, in bytes of a frame's h w:  A (Y) + (A + S (N - 1)) / 2 (U, V) + S / 2 (averages) + 3 S (N - 1) (the shifted
+ * clips, tht > 0) + 3 S (the stabilised frames, flicker != 0), plus 24 bytes per shifted frame of tables and sums. */
+typedef struct havc_chroma_stab_params {
+    int width, height, n_frames;  /* width, height: even, 2..4096 */
+    int first_frame;              /* clip index of frame 0 (the n < 15 rule alone; the clip's ends are the array's) */
+    int n_weights;                /* N: odd, 3..15 */
+    int weights[15];              /* _build_avg_arithmetic / _build_avg_weighted; each within -1000..1000 */
+    double sat;
+    int tht;                      /* 0..256; 0: the temporal average alone */
+    int flicker;                  /* != 0: ReduceFlicker behind the stabiliser */
+    double weight, tht_scen;
+    int chunk_frames;             /* output frames per enqueue sequence; 0 = the library's choice */
+    int reserved;
+    const uint8_t* scene_prev;    /* host memory, n_frames bytes, or NULL */
+    const uint8_t* scene_next;
+} havc_chroma_stab_params;
+/* src, dst: host or device pointers like every filter here.  Device operands: the call only enqueues; nothing is read back.  The bytes are identical from
+ * run to run.  A NULL pointer, dst == src, an odd, non-positive or oversized frame, n_weights even or outside 3..15, a negative first_frame / chunk_frames,
+ * tht outside 0..256, a non-finite sat / weight / tht_scen: HAVC_E_INVALID, nothing runs. */
+int havc_chroma_stab_clip(havc_ctx* ctx, const uint8_t* src, uint8_t* dst, const havc_chroma_stab_params* params);
+/* the frame-level decision of the call above, on the host (no context, no GPU): out[0] = the weight restore_color gets, out[1] = 1 when the tht_scen gate
+ * leaves the frame as it is.  sum_y: sum of cv2's Y over the shifted clip's frame; gray_count: its pixels with S < tht. */
+int havc_chroma_stab_frame_params(int64_t sum_y, int64_t gray_count, int64_t n_pixels, double weight, double tht_scen, double* out);
+/* the ReduceFlicker stand-in above on its own (HAVC_stabilizer runs it behind stab_p's hue adjustment): any frame size up to 2^30 pixels; dst != src */
+int havc_reduce_flicker_clip(havc_ctx* ctx, const uint8_t* src, uint8_t* dst, int width, int height, int n_frames);
 /* HAVC_adjust_rgb (vsdeoldify/__init__.py:1342-1374 -> vs_rgb_normalize, vsslib/vsfilters.py:1013-1038, and adjust_rgb, havc_utils.py:664-749) on a clip: every
  * stage is a function of the sample's own value and the frame's three channel means, so the call is three launches -- the channel sums (normalize != 0),
  * 3 x 256 bytes per frame composed on the device in float64, one pass that applies them -- and nothing is read back.

@@ -108,6 +108,14 @@ class TweakParams(C.Structure):
                 ("luma_lut", C.c_uint8 * 256)]
 
 
+class ChromaStabParams(C.Structure):
+    """`havc_chroma_stab_params` (include/havc_mi355.h): clip size, first frame number, the AverageFrames weights, restore_color's arguments, the flicker
+    switch, the chunk size and the two scene-change arrays of havc_chroma_stab_clip"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int), ("first_frame", C.c_int), ("n_weights", C.c_int), ("weights", C.c_int * 15),
+                ("sat", C.c_double), ("tht", C.c_int), ("flicker", C.c_int), ("weight", C.c_double), ("tht_scen", C.c_double), ("chunk_frames", C.c_int),
+                ("reserved", C.c_int), ("scene_prev", C.c_void_p), ("scene_next", C.c_void_p)]
+
+
 class AdjustParams(C.Structure):
     """`havc_adjust_params` (include/havc_mi355.h): clip size, normalisation, the affine step and the per-plane gamma tables of havc_adjust_rgb_clip"""
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int), ("normalize", C.c_int), ("strength", C.c_double), ("gain", C.c_float * 3),
@@ -208,6 +216,9 @@ SYMBOLS = [
     ("havc_rgb_to_yuv420", _I, [_P, _P, _P, _P, _P, _I, _I, _I]),
     ("havc_yuv420_to_rgb", _I, [_P, _P, _P, _P, _P, _I, _I, _I]),
     ("havc_tweak_weights", _I, [_P]),
+    ("havc_chroma_stab_clip", _I, [_P, _P, _P, _P]),
+    ("havc_chroma_stab_frame_params", _I, [C.c_int64, C.c_int64, C.c_int64, _D, _D, _P]),
+    ("havc_reduce_flicker_clip", _I, [_P, _P, _P, _I, _I, _I]),
     ("havc_adjust_rgb_clip", _I, [_P, _P, _P, _P]),
     ("havc_adjust_frame_params", _I, [_P, C.c_int64, _P]),
     ("havc_luma_lut", _I, [_P, _P, _P, _P, _I, _I]),

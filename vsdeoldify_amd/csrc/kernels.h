@@ -267,6 +267,36 @@ struct TweakFwdArgs {
 struct TweakBackArgs { int n, h, w; TweakWeights wt; };
 int launch_tweak_forward(const uint8_t* src, uint8_t* y, uint8_t* u, uint8_t* v, TweakFwdArgs a, hipStream_t s);
 int launch_tweak_back(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint8_t* dst, TweakBackArgs a, hipStream_t s);
+// the two variants havc_chroma_stab_clip needs (same kernel bodies): the back conversion with Y of frame yidx[f] and U, V of frame cidx[f] (device tables
+// of a.n entries), and the forward conversion of restore_color(color frame color_idx[f], gray frame f) that keeps U and V only
+struct TweakRestoreArgs {
+    const uint8_t* color;                 // the clip the colours come from; frame color_idx[f] belongs to gray frame f
+    const int* color_idx;
+    const uint8_t* mode;                  // per frame: 0 = the gray frame as it is (clip frame < 15), 1 = restore_color with its gate
+    const unsigned long long* stats;      // per frame: sum of cv2's Y, count of pixels with S < tht (launch_stab_stats)
+    double sat, weight, tht_scen;
+    int tht;
+};
+int launch_tweak_back_indexed(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint8_t* dst, const int* yidx, const int* cidx, TweakBackArgs a,
+                              hipStream_t s);
+int launch_tweak_forward_restore(const uint8_t* gray, uint8_t* u, uint8_t* v, TweakFwdArgs a, TweakRestoreArgs ra, hipStream_t s);
+// chroma_stab.hip: what HAVC_stabilizer(stab=True) adds around those -- the index tables of a chunk, the per-frame sums of the shifted clips,
+// std.AverageFrames on the U / V planes, ReduceFlicker (vsslib/vsfilters.py:38-63, 84-157, 216-356; the stand-ins of tests/stab_util.py)
+struct StabTableArgs {
+    int S, s0;                            // frames the chunk stabilises: clip frames s0 .. s0 + S - 1
+    int A, a0;                            // source frames of the chunk: a0 .. a0 + A - 1 (at most 1024)
+    int last, first_frame;                // last frame of the clip; clip index of frame 0 (the n < 15 rule)
+    int N, restore;                       // weights; restore != 0: tht > 0 (list form over restored clips), 0: temporal form with the scene walk
+    uint32_t prev_bits[32], next_bits[32];   // bit i: source frame a0 + i carries _SceneChangePrev / _SceneChangeNext
+};
+// pair_y / pair_c / pair_mode: S * (N - 1) entries (restore != 0); avg_tab: S * N plane numbers of the U / V pools
+int launch_stab_tables(StabTableArgs a, int* pair_y, int* pair_c, uint8_t* pair_mode, int* avg_tab, hipStream_t s);
+// stats: 2 * n zero-filled slots; frames with mode[f] == 0 are skipped
+int launch_stab_stats(const uint8_t* gray, const uint8_t* mode, unsigned long long* stats, int n, int h, int w, int tht, hipStream_t s);
+struct StabAverageArgs { int S, N, weights[15]; int64_t plane_bytes; };
+int launch_stab_average(const uint8_t* upool, const uint8_t* vpool, uint8_t* uo, uint8_t* vo, const int* avg_tab, StabAverageArgs a, hipStream_t s);
+// frames: clip frames t0 .. of the stabilised clip (every frame n - 2 .. n + 2 of an interior output frame is among them); out: frames f0 .. f0 + count - 1
+int launch_reduce_flicker(const uint8_t* frames, int t0, uint8_t* out, int f0, int count, int last, int64_t frame_bytes, hipStream_t s);
 struct AdjustArgs {
     int n, h, w;
     int mode;                     // 0: no normalisation, 1: vs_rgb_normalize, 2: std.Merge(clip, normalised, strength)
@@ -329,6 +359,7 @@ void preload_scedge();
 void preload_equalize();
 void preload_retinex();
 void preload_tweak_clip();
+void preload_chroma_stab();
 void preload_ddcolor();
 void preload_colormnet();
 void preload_colormnet_net();

@@ -6,6 +6,7 @@
 #include "equalize_ops.h"
 #include "retinex_ops.h"
 #include "tweak_ops.h"
+#include "chroma_stab_ops.h"
 
 extern "C" {
 
@@ -641,6 +642,129 @@ int havc_tweak_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const havc_tw
         if (!e) e = launch_tweak_back(d_y, d_u, d_v, d_dst + (size_t)f0 * fb, ba, c->stream);
         c->stats.launches += 2;
         if (e) return hip_fail(c, (hipError_t)e, "tweak_clip");
+    }
+    return stage_out(c, dst, d_dst, cb, host);
+}
+
+// ---- HAVC_stabilizer(stab=True): vs_chroma_stabilizer_ex + vs_reduce_flicker on a clip, chunk by chunk (chroma_stab.hip, tweak.hip) ----
+static_assert(sizeof(havc_chroma_stab_params) == 136, "havc_chroma_stab_params layout");
+
+int havc_chroma_stab_frame_params(int64_t sum_y, int64_t gray_count, int64_t n_pixels, double weight, double tht_scen, double* out) {
+    if (sum_y < 0 || gray_count < 0 || n_pixels <= 0 || gray_count > n_pixels || !out || !std::isfinite(weight) || !std::isfinite(tht_scen)) return HAVC_E_INVALID;
+    double eff;
+    const bool gate = cs_frame_decision((unsigned long long)sum_y, (unsigned long long)gray_count, n_pixels, weight, tht_scen, eff);
+    out[0] = eff;
+    out[1] = gate ? 1.0 : 0.0;
+    return HAVC_OK;
+}
+
+// Frames a chunk stabilises (its output frames plus, with flicker, two on either side).  The shifted clips of a chunk stay under 512 MiB (at 256 MiB a 64-frame clip at 384 x 384 with N = 15 went through in two chunks, and each chunk pays the
+// back kernel's latency again -- it is one block per frame: 5.67 ms a call against one chunk's figure in profiles/chroma_stab.txt); a chunk's source
+// window (those frames and (N - 1) / 2 on either side) holds at most CS_MAX_WINDOW frames, and its N - 1 shifted clips at most 65535 frames (one launch).
+static int chroma_stab_span(const havc_chroma_stab_params* p, int halo) {
+    const int64_t fb = (int64_t)p->width * p->height * 3;
+    const int64_t by_bytes = std::max<int64_t>(1, ((int64_t)512 << 20) / ((int64_t)(p->n_weights - 1) * fb));
+    int64_t span = std::min<int64_t>(by_bytes, CS_MAX_WINDOW - (p->n_weights - 1));
+    span = std::min<int64_t>(span, 65535 / (p->n_weights - 1));
+    if (p->chunk_frames > 0) span = std::min<int64_t>(span, (int64_t)p->chunk_frames + 2 * halo);
+    return (int)std::max<int64_t>(span, 2 * halo + 1);
+}
+
+int havc_chroma_stab_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const havc_chroma_stab_params* p) {
+    if (!c || !src || !dst || !p) return fail(c, HAVC_E_INVALID, "chroma_stab_clip: bad args");
+    if (src == dst) return fail(c, HAVC_E_INVALID, "chroma_stab_clip: dst must not be src (every output frame reads its neighbours)");
+    int rc = tweak_size_check(c, "chroma_stab_clip", p->width, p->height, p->n_frames);
+    if (rc) return rc;
+    if (p->n_weights < 3 || p->n_weights > CS_MAX_WEIGHTS || !(p->n_weights & 1)) return fail(c, HAVC_E_INVALID, "chroma_stab_clip: n_weights must be odd and 3..15");
+    for (int k = 0; k < p->n_weights; ++k)
+        if (p->weights[k] < -1000 || p->weights[k] > 1000) return fail(c, HAVC_E_INVALID, "chroma_stab_clip: a weight is outside -1000..1000");
+    if (p->first_frame < 0 || p->chunk_frames < 0) return fail(c, HAVC_E_INVALID, "chroma_stab_clip: first_frame and chunk_frames must be >= 0");
+    if (p->tht < 0 || p->tht > 256 || !(std::isfinite(p->sat) && std::isfinite(p->weight) && std::isfinite(p->tht_scen)))
+        return fail(c, HAVC_E_INVALID, "chroma_stab_clip: tht must be 0..256, sat / weight / tht_scen finite");
+    if ((p->scene_prev && is_device_ptr(p->scene_prev)) || (p->scene_next && is_device_ptr(p->scene_next)))
+        return fail(c, HAVC_E_INVALID, "chroma_stab_clip: the scene-change arrays are host memory");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    const int n = p->n_frames, N = p->n_weights, nh = (N - 1) / 2, halo = p->flicker ? 2 : 0, last = n - 1;
+    const bool restore = p->tht > 0;
+    const int span = chroma_stab_span(p, halo), core = span - 2 * halo;
+    const size_t pb = (size_t)p->width * p->height, qb = pb / 4, fb = pb * 3, cb = (size_t)n * fb;
+    const size_t S_max = (size_t)std::min(span, n), A_max = std::min<size_t>(S_max + 2 * nh, (size_t)n), P_max = restore ? S_max * (N - 1) : 0;
+    // the chunk's workspace, one allocation: Y planes | U pool | V pool (source planes, then the restored clips') | averaged U, V | the shifted clips |
+    // the stabilised frames in front of the flicker pass | tables | sums
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    size_t off = 0;
+    auto take = [&](size_t nb) { const size_t at = off; off += up(nb); return at; };
+    const size_t o_y = take(A_max * pb), o_u = take((A_max + P_max) * qb), o_v = take((A_max + P_max) * qb), o_au = take(S_max * qb), o_av = take(S_max * qb);
+    const size_t o_pairs = take(P_max * fb), o_t = take(p->flicker ? S_max * fb : 0), o_py = take(P_max * sizeof(int)), o_pc = take(P_max * sizeof(int));
+    const size_t o_tab = take(S_max * N * sizeof(int)), o_mode = take(P_max), o_stats = take(P_max * 2 * sizeof(unsigned long long));
+    const uint8_t* d_src;
+    uint8_t* d_dst;
+    bool host;
+    if ((rc = stage_in(c, SCR_IN, src, cb, &d_src)) || (rc = stage_out_ptr(c, SCR_OUT, dst, cb, &d_dst, &host)) || (rc = ensure_scratch(c, SCR_CHROMA_STAB, off))) return rc;
+    uint8_t* ws = (uint8_t*)c->scratch[SCR_CHROMA_STAB];
+    uint8_t *d_y = ws + o_y, *d_u = ws + o_u, *d_v = ws + o_v, *d_au = ws + o_au, *d_av = ws + o_av, *d_pairs = ws + o_pairs, *d_t = ws + o_t, *d_mode = ws + o_mode;
+    int *d_py = (int*)(ws + o_py), *d_pc = (int*)(ws + o_pc), *d_tab = (int*)(ws + o_tab);
+    unsigned long long* d_stats = (unsigned long long*)(ws + o_stats);
+    TweakFwdArgs fa{};
+    fa.h = p->height; fa.w = p->width;
+    TweakBackArgs ba{};
+    ba.h = p->height; ba.w = p->width;
+    StabAverageArgs aa{};
+    aa.N = N; aa.plane_bytes = (int64_t)qb;
+    for (int k = 0; k < N; ++k) aa.weights[k] = p->weights[k];
+    for (int f0 = 0; f0 < n; f0 += core) {
+        const int f1 = std::min(f0 + core, n), s0 = std::max(f0 - halo, 0), s1 = std::min(f1 + halo, n), S = s1 - s0;
+        const int a0 = std::max(s0 - nh, 0), a1 = std::min(s1 + nh, n), A = a1 - a0, P = restore ? S * (N - 1) : 0;
+        StabTableArgs ta{};
+        ta.S = S; ta.s0 = s0; ta.A = A; ta.a0 = a0; ta.last = last; ta.first_frame = p->first_frame; ta.N = N; ta.restore = restore;
+        for (int i = 0; i < A; ++i) {
+            if (p->scene_prev && p->scene_prev[a0 + i]) ta.prev_bits[i >> 5] |= 1u << (i & 31);
+            if (p->scene_next && p->scene_next[a0 + i]) ta.next_bits[i >> 5] |= 1u << (i & 31);
+        }
+        int e = launch_stab_tables(ta, d_py, d_pc, d_mode, d_tab, c->stream);
+        fa.n = A;
+        if (!e) e = launch_tweak_forward(d_src + (size_t)a0 * fb, d_y, d_u, d_v, fa, c->stream);
+        c->stats.launches += 2;
+        if (!e && restore) {
+            ba.n = P;
+            e = launch_tweak_back_indexed(d_y, d_u, d_v, d_pairs, d_py, d_pc, ba, c->stream);
+            if (!e) e = (int)hipMemsetAsync(d_stats, 0, (size_t)P * 2 * sizeof(unsigned long long), c->stream);
+            if (!e) e = launch_stab_stats(d_pairs, d_mode, d_stats, P, p->height, p->width, p->tht, c->stream);
+            TweakRestoreArgs ra{};
+            ra.color = d_src + (size_t)a0 * fb; ra.color_idx = d_py; ra.mode = d_mode; ra.stats = d_stats;
+            ra.sat = p->sat; ra.weight = p->weight; ra.tht_scen = p->tht_scen; ra.tht = p->tht;
+            fa.n = P;
+            if (!e) e = launch_tweak_forward_restore(d_pairs, d_u + (size_t)A * qb, d_v + (size_t)A * qb, fa, ra, c->stream);
+            c->stats.launches += 3;
+        }
+        aa.S = S;
+        if (!e) e = launch_stab_average(d_u, d_v, d_au, d_av, d_tab, aa, c->stream);
+        ba.n = S;
+        if (!e) e = launch_tweak_back(d_y + (size_t)(s0 - a0) * pb, d_au, d_av, p->flicker ? d_t : d_dst + (size_t)s0 * fb, ba, c->stream);
+        c->stats.launches += 2;
+        if (!e && p->flicker) { e = launch_reduce_flicker(d_t, s0, d_dst + (size_t)f0 * fb, f0, f1 - f0, last, (int64_t)fb, c->stream); c->stats.launches++; }
+        if (e) return hip_fail(c, (hipError_t)e, "chroma_stab_clip");
+    }
+    return stage_out(c, dst, d_dst, cb, host);
+}
+
+int havc_reduce_flicker_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, int width, int height, int n_frames) {
+    if (!c || !src || !dst || width <= 0 || height <= 0 || n_frames <= 0 || (int64_t)width * height > ((int64_t)1 << 30))
+        return fail(c, HAVC_E_INVALID, "reduce_flicker_clip: bad args (at most 2^30 pixels per frame)");
+    if (src == dst) return fail(c, HAVC_E_INVALID, "reduce_flicker_clip: dst must not be src (every output frame reads its neighbours)");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(c, hipSetDevice(c->dev));
+    const size_t fb = (size_t)width * height * 3, cb = (size_t)n_frames * fb;
+    int rc;
+    const uint8_t* d_src;
+    uint8_t* d_dst;
+    bool host;
+    if ((rc = stage_in(c, SCR_IN, src, cb, &d_src)) || (rc = stage_out_ptr(c, SCR_OUT, dst, cb, &d_dst, &host))) return rc;
+    for (int f0 = 0; f0 < n_frames; f0 += 65535) {
+        const int e = launch_reduce_flicker(d_src, 0, d_dst + (size_t)f0 * fb, f0, std::min(65535, n_frames - f0), n_frames - 1, (int64_t)fb, c->stream);
+        c->stats.launches++;
+        if (e) return hip_fail(c, (hipError_t)e, "reduce_flicker_clip");
     }
     return stage_out(c, dst, d_dst, cb, host);
 }

@@ -18,6 +18,10 @@
 //                            KEPT: bands one after the other, one walking wave per plane, 16 waves staging (7.7 ms for 64 frames of 1080p).  REJECTED:
 //                            a block of the three walking waves alone (18.8 ms: the staging passes waited for their own global loads).  Pipelining
 //                            several bands of a plane across the waves of a block was not built (profiles/tweak.txt, DESIGN.md section 4 "Tweak").
+//     tweak_back_indexed_kernel, tweak_forward_restore_kernel   the same two bodies for havc_chroma_stab_clip (chroma_stab.hip): the back conversion with Y of
+//                            frame yidx[f] and U, V of frame cidx[f] (the shifted clips of vs_get_clip_frame need no gathered planes), and the forward one
+//                            with restore_color's pixel (pixel_ops.h) computed in the load, U and V stored only.  The templates leave the plain kernels'
+//                            code as it was.
 //     adjust_tables_kernel   HAVC_adjust_rgb is a function of the sample's own value and the frame's channel means: normalise (gain from the means),
 //                            std.Merge by strength, "x r * rb +", gamma.  One block per frame composes the 3 x 256 bytes from the channel sums in float64;
 //                            nothing is read back.
@@ -25,6 +29,8 @@
 #include "kernels.h"
 #include "equalize_ops.h"
 #include "tweak_ops.h"
+#include "pixel_ops.h"
+#include "chroma_stab_ops.h"
 
 // ---- forward ------------------------------------------------------------------------------------------------------------------------------------------------
 #define TWF_TH 16                                  // chroma rows of a tile
@@ -34,8 +40,12 @@
 #define TWF_PITCH (TWF_LW + 1)
 #define TWF_THREADS 256
 
-__global__ void __launch_bounds__(TWF_THREADS) tweak_forward_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ yp, uint8_t* __restrict__ up,
-                                                                   uint8_t* __restrict__ vp, TweakFwdArgs a) {
+// RESTORE (havc_chroma_stab_clip, chroma_stab.hip): frame f of `src` is a shifted clip's frame; what enters the matrix is restore_color's pixel (pixel_ops.h
+// restore_binary_pixel) of it and of frame color_idx[f] of ra.color, unless the frame passes as it is (mode[f] == 0, or the tht_scen gate taken from the
+// frame's two integer sums: chroma_stab_ops.h, block-uniform).  The restored frame exists in registers only; Y is not stored.
+template <bool RESTORE>
+__device__ __forceinline__ void tweak_forward_body(const uint8_t* __restrict__ src, uint8_t* __restrict__ yp, uint8_t* __restrict__ up,
+                                                   uint8_t* __restrict__ vp, const TweakFwdArgs& a, const TweakRestoreArgs& ra) {
     __shared__ float cc[2][TWF_LH][TWF_PITCH];     // Cb, Cr of the tile and its halo
     __shared__ float vv[2][TWF_TH][TWF_PITCH];     // after the vertical pass
     __shared__ float unit[256];                    // sample / 255
@@ -48,17 +58,34 @@ __global__ void __launch_bounds__(TWF_THREADS) tweak_forward_kernel(const uint8_
     lum[t] = a.has_luma ? a.luma_lut[t] : (uint8_t)t;
     __syncthreads();
     const uint8_t* frame = src + (int64_t)f * h * w * 3;
-    uint8_t* yf = yp + (int64_t)f * h * w;
+    uint8_t* yf = RESTORE ? nullptr : yp + (int64_t)f * h * w;
+    const uint8_t* cframe = nullptr;
+    bool restore = false;
+    double rweight = 0.0;
+    if constexpr (RESTORE) {
+        cframe = ra.color + (int64_t)ra.color_idx[f] * h * w * 3;
+        if (ra.mode[f]) restore = !cs_frame_decision(ra.stats[2 * f], ra.stats[2 * f + 1], (long long)h * w, ra.weight, ra.tht_scen, rweight);
+    }
     for (int idx = t; idx < TWF_LH * TWF_LW; idx += TWF_THREADS) {
         const int ly = idx / TWF_LW, lx = idx - ly * TWF_LW;
         const int py = 2 * j0 + TW_DOWN_FIRST + ly, px = 2 * i0 + TW_DOWN_FIRST + lx;
         float cb = 0.f, cr = 0.f;
         if (py < h + TW_DOWN_TAPS && px < w + TW_DOWN_TAPS) {                 // beyond that no sample of the plane has a tap
             const int my = tw_mirror(py, h), mx = tw_mirror(px, w);
-            const uint8_t* p = frame + ((int64_t)my * w + mx) * 3;
+            const int64_t po = ((int64_t)my * w + mx) * 3;
+            const uint8_t* p = frame + po;
+            int px3[3] = {p[0], p[1], p[2]};
+            if constexpr (RESTORE) {
+                if (restore) {
+                    const uint8_t* q = cframe + po;
+                    int o[3];
+                    restore_binary_pixel(q[0], q[1], q[2], px3[0], px3[1], px3[2], ra.sat, ra.tht, rweight, 0, o);
+                    px3[0] = o[0]; px3[1] = o[1]; px3[2] = o[2];
+                }
+            }
             float y;
-            tw_rgb2ycc(unit[gam[p[0]]], unit[gam[p[1]]], unit[gam[p[2]]], y, cb, cr);
-            if (my == py && mx == px && ly >= -TW_DOWN_FIRST && ly < -TW_DOWN_FIRST + 2 * TWF_TH && lx >= -TW_DOWN_FIRST && lx < -TW_DOWN_FIRST + 2 * TWF_TW)
+            tw_rgb2ycc(unit[gam[px3[0]]], unit[gam[px3[1]]], unit[gam[px3[2]]], y, cb, cr);
+            if (!RESTORE && my == py && mx == px && ly >= -TW_DOWN_FIRST && ly < -TW_DOWN_FIRST + 2 * TWF_TH && lx >= -TW_DOWN_FIRST && lx < -TW_DOWN_FIRST + 2 * TWF_TW)
                 yf[(int64_t)py * w + px] = lum[tw_quant_y(y)];
         }
         cc[0][ly][lx] = cb;
@@ -94,11 +121,30 @@ __global__ void __launch_bounds__(TWF_THREADS) tweak_forward_kernel(const uint8_
     }
 }
 
+__global__ void __launch_bounds__(TWF_THREADS) tweak_forward_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ yp, uint8_t* __restrict__ up,
+                                                                   uint8_t* __restrict__ vp, TweakFwdArgs a) {
+    tweak_forward_body<false>(src, yp, up, vp, a, TweakRestoreArgs{});
+}
+__global__ void __launch_bounds__(TWF_THREADS) tweak_forward_restore_kernel(const uint8_t* __restrict__ gray, uint8_t* __restrict__ up, uint8_t* __restrict__ vp,
+                                                                           TweakFwdArgs a, TweakRestoreArgs ra) {
+    tweak_forward_body<true>(gray, nullptr, up, vp, a, ra);
+}
+
 int launch_tweak_forward(const uint8_t* src, uint8_t* y, uint8_t* u, uint8_t* v, TweakFwdArgs a, hipStream_t s) {
     if (a.n <= 0 || a.n > 65535 || a.h < 2 || a.w < 2 || (a.h & 1) || (a.w & 1) || a.h > TW_MAX_SIDE || a.w > TW_MAX_SIDE) return (int)hipErrorInvalidValue;
     tw_all_weights(a.wt);
     const dim3 grid((unsigned)((a.w / 2 + TWF_TW - 1) / TWF_TW), (unsigned)((a.h / 2 + TWF_TH - 1) / TWF_TH), (unsigned)a.n);
     hipLaunchKernelGGL(tweak_forward_kernel, grid, dim3(TWF_THREADS), 0, s, src, y, u, v, a);
+    return (int)hipGetLastError();
+}
+
+// gray: a.n frames; U and V of frame f go to u / v + f * (h / 2) * (w / 2).  The tables of a are off (identity).
+int launch_tweak_forward_restore(const uint8_t* gray, uint8_t* u, uint8_t* v, TweakFwdArgs a, TweakRestoreArgs ra, hipStream_t s) {
+    if (a.n <= 0 || a.n > 65535 || a.h < 2 || a.w < 2 || (a.h & 1) || (a.w & 1) || a.h > TW_MAX_SIDE || a.w > TW_MAX_SIDE) return (int)hipErrorInvalidValue;
+    a.has_gamma = a.has_luma = a.has_hue_sat = false;
+    tw_all_weights(a.wt);
+    const dim3 grid((unsigned)((a.w / 2 + TWF_TW - 1) / TWF_TW), (unsigned)((a.h / 2 + TWF_TH - 1) / TWF_TH), (unsigned)a.n);
+    hipLaunchKernelGGL(tweak_forward_restore_kernel, grid, dim3(TWF_THREADS), 0, s, gray, u, v, a, ra);
     return (int)hipGetLastError();
 }
 
@@ -117,8 +163,10 @@ __device__ __forceinline__ float tw_from_lane_above(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, false));
 }
 
-__global__ void __launch_bounds__(TWB_THREADS) tweak_back_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ up, const uint8_t* __restrict__ vp,
-                                                                uint8_t* __restrict__ dst, TweakBackArgs a) {
+// INDEXED (havc_chroma_stab_clip's shifted clips): output frame f takes Y from frame yidx[f] and U, V from frame cidx[f] of the planes
+template <bool INDEXED>
+__device__ __forceinline__ void tweak_back_body(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ up, const uint8_t* __restrict__ vp,
+                                                uint8_t* __restrict__ dst, const TweakBackArgs& a, const int* __restrict__ yidx, const int* __restrict__ cidx) {
     __shared__ float erow[3][TW_MAX_SIDE];         // the error row a band hands to the next one, per channel
     __shared__ float xs[3][TWB_ROWS][TWB_XP];      // the chunk's samples: xs[c][l][j] = channel c at row r0 + l, column t0 - 2 l + j
     __shared__ float vb[2][TWB_ROWS][TWB_VP];      // Cb, Cr after the vertical pass: vb[p][l][jj] = chroma column (t0 / 2 - l) - 1 + jj
@@ -128,8 +176,9 @@ __global__ void __launch_bounds__(TWB_THREADS) tweak_back_kernel(const uint8_t* 
     const bool walker = (tid >> 6) < 3;            // wave-uniform
     const int c = walker ? tid >> 6 : 0;
     const int h = a.h, w = a.w, ch = h >> 1, cw = w >> 1;
-    const uint8_t* yf = yp + (int64_t)f * h * w;
-    const uint8_t* cf[2] = {up + (int64_t)f * ch * cw, vp + (int64_t)f * ch * cw};
+    const int fy = INDEXED ? yidx[f] : f, fc = INDEXED ? cidx[f] : f;
+    const uint8_t* yf = yp + (int64_t)fy * h * w;
+    const uint8_t* cf[2] = {up + (int64_t)fc * ch * cw, vp + (int64_t)fc * ch * cw};
     uint8_t* df = dst + (int64_t)f * h * w * 3;
     if (tid < 256) { unit[tid] = (float)tid / 255.f; cunit[tid] = ((float)tid - 128.f) / 255.f; }
     for (int i = tid; i < 3 * w; i += TWB_THREADS) erow[i / w][i % w] = 0.f;
@@ -220,6 +269,24 @@ __global__ void __launch_bounds__(TWB_THREADS) tweak_back_kernel(const uint8_t* 
             }
         }
     }
+}
+
+__global__ void __launch_bounds__(TWB_THREADS) tweak_back_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ up, const uint8_t* __restrict__ vp,
+                                                                uint8_t* __restrict__ dst, TweakBackArgs a) {
+    tweak_back_body<false>(yp, up, vp, dst, a, nullptr, nullptr);
+}
+__global__ void __launch_bounds__(TWB_THREADS) tweak_back_indexed_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ up,
+                                                                        const uint8_t* __restrict__ vp, uint8_t* __restrict__ dst, TweakBackArgs a,
+                                                                        const int* __restrict__ yidx, const int* __restrict__ cidx) {
+    tweak_back_body<true>(yp, up, vp, dst, a, yidx, cidx);
+}
+
+int launch_tweak_back_indexed(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint8_t* dst, const int* yidx, const int* cidx, TweakBackArgs a,
+                              hipStream_t s) {
+    if (a.n <= 0 || a.h < 2 || a.w < 2 || (a.h & 1) || (a.w & 1) || a.h > TW_MAX_SIDE || a.w > TW_MAX_SIDE || !yidx || !cidx) return (int)hipErrorInvalidValue;
+    tw_all_weights(a.wt);
+    hipLaunchKernelGGL(tweak_back_indexed_kernel, dim3((unsigned)a.n), dim3(TWB_THREADS), 0, s, y, u, v, dst, a, yidx, cidx);
+    return (int)hipGetLastError();
 }
 
 int launch_tweak_back(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint8_t* dst, TweakBackArgs a, hipStream_t s) {

@@ -23,7 +23,7 @@ Same names, argument lists, defaults, parameter normalisation, frame-size rule, 
 behind `HAVC_colorizer` (models and nets are built once and reused between calls).
 
 What only VapourSynth can do stays there and is REFUSED here instead of being approximated: `vs_tweak` (deoldify / ddcolor
-sat / hue other than 1 / 0, `luma_mask_sat` < 1), the temporal half of HAVC_stabilizer (`stab=True`), scene detection INSIDE HAVC_colorizer / HAVC_ddeoldify (`sc_threshold` > 0, `sc_min_freq` > 0: the reference-frame
+sat / hue other than 1 / 0, `luma_mask_sat` < 1), scene detection INSIDE HAVC_colorizer / HAVC_ddeoldify (`sc_threshold` > 0, `sc_min_freq` > 0: the reference-frame
 logic of vs_sc_ddcolor / vs_sc_tweak that hangs off it), the SSIM post-filter INSIDE HAVC_SceneDetect (`sc_tht_ssim` in (0, 1), `sc_min_int` > 1: that refusal is pinned and
 stays; the filter itself is built and runs in HAVC_extract_reference_frames), the plugin scene detectors of HAVC_extract_reference_frames (`sc_algo` 1-3; 1 is built as HAVC_SceneDetectEdges but not routed there yet), of HAVC_deepex the exemplar models 1-3 (Deep-Exemplar, DeepRemaster: not built), methods 1-6
 (reference frames from a directory or a video), `encode_mode` 2 and `sc_framedir` / `only_ref_frames` (they write files), the parts of the DDColor
@@ -66,8 +66,7 @@ contract; none of it can be executed where the fixtures are made
     full range; Mitchell bicubic chroma resampling, `dither_type="error_diffusion"` on the way back), `std.Levels(gamma=)`, `std.Expr`, `std.Lut` -> the
     float32 sequences of tests/tweak_util.py, which csrc/tweak.hip equals byte for byte; none of it can be executed where the fixtures are made.  What
     vs_tweak, adjust_rgb, vs_rgb_normalize and rgb_denoise hand to those filters is the reference's Python, restated and pinned by tests/golden/tweak.npz.
-    The `vs_tweak` refusals INSIDE the other entry points (HAVC_colorizer's sat / hue, HAVC_DeepRemaster / HAVC_restore_video render_vivid, ddtweak,
-    HAVC_stabilizer(stab=True)) stay exactly as they are: existing tests pin them, and routing them to the new code is a separate decision.
+    The `vs_tweak` refusals INSIDE the other entry points (HAVC_colorizer's sat / hue, HAVC_DeepRemaster / HAVC_restore_video render_vivid, ddtweak) stay exactly as they are: existing tests pin them, and routing them to the new code is a separate decision.
 HAVC_clip_slice pads where the reference's std.CropAbs would leave the padded clip by one pixel (an odd width / height with overlap 0: VapourSynth
 raises there); every other geometry CropAbs refuses -- an overlap >= the base tile, a negative overlap -- is refused with HAVCError.
 
@@ -567,16 +566,41 @@ def HAVC_stabilizer(clip, dark=False, dark_p=(0.2, 0.8), smooth=False, smooth_p=
     """vsdeoldify/__init__.py:2748-2751: the colour filters every HAVC_main preset ends in, at reduced resolution -- Spline64 squash to
     frame_size x frame_size (the library's Spline64, the stand-in of zimg's everywhere in this file), dark -> smooth -> colormap in ONE launch
     (stabilizer.stabilize_np), Spline64 back + the luma of the source (_clip_chroma_resize).  ndarray in -> ndarray out; DeviceImage in -> DeviceImage out
-    (nothing leaves HBM, the call only enqueues).  stab=True is refused: see below."""
+    (nothing leaves HBM, the call only enqueues).  stab=True (a clip only) adds vs_chroma_stabilizer_ex and vs_reduce_flicker behind the three
+    (chroma_stab.stab_stage_np: havc_chroma_stab_clip; the stand-ins of zimg, std.AverageFrames and ReduceFlicker are defined by tests/stab_util.py).  Arrays
+    carry no frame props, and this function keeps the reference's argument list: the clip is taken to have no scene changes; HAVC_stabilizer_scenes below
+    is the same call with the SceneInfo of the clip.  Frame 0 of the operand is clip frame 0 (vs_sc_recover_clip_color's `n < 15`)."""
+    return _stabilizer(clip, dark, dark_p, smooth, smooth_p, stab, stab_p, colormap, render_factor, device_index, None)
+
+
+def HAVC_stabilizer_scenes(clip, scenes, dark=False, dark_p=(0.2, 0.8), smooth=False, smooth_p=(0.3, 0.7, 0.9, 0.0, "none"), stab=False,
+                           stab_p=(5, 'A', 1, 15, 0.2, 0.8), colormap="none", render_factor=24, device_index=0):
+    """HAVC_stabilizer on a clip whose scene changes are known: `scenes` is the SceneInfo of the clip (HAVC_SceneDetect's result for it, as in
+    HAVC_export_reference_frames), what the reference's std.AverageFrames(scenechange=True) reads off every frame as _SceneChangePrev / _SceneChangeNext
+    (stab=True with tht = stab_p[3] = 0, vs_clip_color_stabilizer; no other stage looks at them).  None = no scene changes."""
+    return _stabilizer(clip, dark, dark_p, smooth, smooth_p, stab, stab_p, colormap, render_factor, device_index, scenes)
+
+
+def _stabilizer(clip, dark, dark_p, smooth, smooth_p, stab, stab_p, colormap, render_factor, device_index, scenes):
     if clip is None or not (is_device(clip) or isinstance(clip, np.ndarray)):
         raise HAVCError("HAVC_stabilizer: this is not a clip")
-    if stab:                                                                                      # __init__.py:2862-2866
-        raise NotImplementedError("HAVC_stabilizer(stab=True): vs_chroma_stabilizer_ex is VapourSynth glue -- a zimg YUV420P8 round trip with error-diffusion "
-                                  "dither, std.AverageFrames driven by scene-change props and the ReduceFlicker plugin (vsfilters.py:84-115, 216-242): "
-                                  "not in this harness")
+    if stab and clip.ndim == 3:                                                                   # __init__.py:2862-2866
+        raise NotImplementedError("HAVC_stabilizer(stab=True): vs_chroma_stabilizer_ex averages every frame with up to 14 neighbours and vs_reduce_flicker "
+                                  "reads two frames on either side: a lone image [h, w, 3] has none -- pass a clip [n, h, w, 3]")
     clip, single = _as_clip(clip)
     n, h, w, _ = clip.shape
     _, fs = _stabilizer_frame_size(render_factor, w)
+    if stab:                                                                                      # __init__.py:2834-2846
+        from . import chroma_stab
+        if len(stab_p) < 6:
+            raise HAVCError("HAVC_stabilizer: stab_p needs (nframes, mode, sat, tht, weight, tht_scen[, hue adjust])")
+        chroma_stab.weight_list(stab_p[0], stab_p[1])                                             # "HybridAVC: unknown average method: ..."
+        if fs % 2:
+            raise HAVCError(f"HAVC_stabilizer(stab=True): frame_size = {fs} is odd: the YUV420 round trip of vs_chroma_stabilizer_ex needs an even width "
+                            f"and height (VapourSynth refuses it too)")
+        if scenes is not None and len(scenes.scene_change_prev) != n:
+            raise HAVCError("HAVC_stabilizer: scenes= must be the SceneInfo of this clip (AverageFrames reads _SceneChangePrev / _SceneChangeNext off "
+                            "every frame)")
     dark_args = smooth_args = None
     if dark:                                                                                      # __init__.py:2806-2813, 2850-2852
         dark_args = (dark_p[0], dark_p[1], (dark_p[2] if len(dark_p) > 2 else "none").lower())
@@ -595,6 +619,8 @@ def HAVC_stabilizer(clip, dark=False, dark_p=(0.2, 0.8), smooth=False, smooth_p=
     ctx = get_context(device_index)
     sq = spline64(ctx, clip, fs, fs)                                                              # __init__.py:2804
     col = stabilize_np(ctx, sq, dark_args, smooth_args, colormap_adjust)
+    if stab:                                                                                      # __init__.py:2862-2866
+        col = chroma_stab.stab_stage_np(ctx, col, stab_p, scenes=scenes)
     out = _clip_chroma_resize(clip, col, device_index)                                            # __init__.py:2868-2869: even when every filter is off
     if single:
         return out.reshaped(out.shape[1:]) if is_device(out) else out[0]
@@ -1169,7 +1195,7 @@ def HAVC_tweak(clip=None, hue=0, sat=1, bright=0, cont=1, gamma=1, *, device_ind
     (tweak.py says what is pinned and what is not); the kernels equal it byte for byte.  The neutral call returns the clip.  One havc_tweak_clip call: two
     launches per chunk of frames.  A frame or a clip; ndarray in -> ndarray out; DeviceImage in -> DeviceImage out (nothing leaves HBM, the call only
     enqueues).  An odd width or height (VapourSynth refuses YUV420 there) and gamma <= 0 are refused.  The vs_tweak refusals inside HAVC_colorizer,
-    HAVC_DeepRemaster, HAVC_restore_video, ddtweak and HAVC_stabilizer(stab=True) stay: routing them here is a separate decision."""
+    HAVC_DeepRemaster, HAVC_restore_video and ddtweak stay: routing them here is a separate decision."""
     from . import tweak
     if not _is_clip(clip):
         raise HAVCError("HAVC_tweak: this is not a clip")

@@ -18,8 +18,8 @@ such an RGB24 clip as limited (:78-82).  An array carries no props, so HAVC_adju
 branch (a bias is scaled by 256 / 235 and checked against +-235), "full" the other (256 / 255, +-255).
 
 `tweak_np`, `adjust_rgb_np`, `rgb_to_yuv420_np`, `yuv420_to_rgb_np` run on a frame [h, w, 3] or a clip [n, h, w, 3], ndarray or DeviceImage; a DeviceImage in
-gives a DeviceImage out and the call only enqueues.  The vs_tweak refusals inside the other entry points (HAVC_colorizer's sat / hue, render_vivid, ddtweak,
-HAVC_stabilizer(stab=True)) stay as they are: routing them here is a separate decision.
+gives a DeviceImage out and the call only enqueues.  The vs_tweak refusals inside the other entry points (HAVC_colorizer's sat / hue, render_vivid, ddtweak) stay as
+they are: routing them here is a separate decision.  HAVC_stabilizer(stab=True) is built on the two conversions (chroma_stab.py).
 """
 import ctypes as C
 import math
