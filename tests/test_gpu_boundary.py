@@ -128,6 +128,25 @@ def test_device_operands_match_host_operands(ctx):
         F.image_luma_np(ctx, dstack_)                       # frame-level statistic: one frame at a time
 
 
+def test_result_of_the_other_kind_and_packs_of_mixed_kinds(ctx):
+    """What the wrappers never ask for (they put a result where the input is) but the C interface allows: host input with a device result and the reverse,
+    several operands of mixed kinds in one scratch slot (the planes of the two YUV halves, the tiles), and two host results of one call (the edge records and
+    their mask tap).  Every combination gives the bytes of the all-host call and counts the same launches."""
+    from tests.operand_kinds_util import calls
+    first = {}
+    for name, label, outs, launches in calls(ctx):
+        print(f"{name} [{label}]: {launches} launches, {[o.nbytes for o in outs]} bytes")
+        assert launches > 0, (name, label)
+        if name not in first:
+            first[name] = (label, outs, launches)                                 # the all-host call
+            continue
+        label0, outs0, launches0 = first[name]
+        assert launches == launches0, (name, label, launches, launches0)
+        for k, (got, want) in enumerate(zip(outs, outs0)):                        # ("no tap" has the records alone: equal to those of the call with a tap)
+            assert got.tobytes() == want.tobytes(), (name, label, label0, k)
+    assert len(first) == 12
+
+
 @pytest.mark.parametrize("pinned,precision", [pytest.param(True, None, id="True"), pytest.param(False, None, id="False"),
                                               pytest.param(True, "precise", id="True-precise"), pytest.param(False, "precise", id="False-precise")])
 def test_pipelined_host_clip_equals_resident_clip(ctx, pinned, precision):

@@ -13,165 +13,116 @@ int havc_memory_read_topk_usage(havc_ctx* c, const float* mk, const float* ms, c
                                 float* usage, int B, int CK, int CV, int N, int HW, int top_k) {
     if (!c || !mk || !qk || !mv || !out || B < 1 || CK < 1 || CV < 1 || N < 1 || HW < 1 || top_k < 1 || top_k > 64)
         return fail(c, HAVC_E_INVALID, "memory_read_topk: bad args (top_k 1..64)");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "memory_read_topk");
     const size_t fmk = (size_t)B * CK * N * 4, fq = (size_t)B * CK * HW * 4, fms = (size_t)B * N * 4, fmv = (size_t)B * CV * N * 4, fo = (size_t)B * CV * HW * 4;
-    const float *d_mk, *d_ms = nullptr, *d_qk, *d_qe = nullptr, *d_mv;
-    uint8_t* d_out;
-    bool host;
-    int rc;
-    if ((rc = stage_in_f(c, SCR_IN, mk, fmk, &d_mk)) || (rc = stage_in_f(c, SCR_IN2, qk, fq, &d_qk)) || (rc = stage_in_f(c, SCR_IN3, mv, fmv, &d_mv)) ||
-        (ms && (rc = stage_in_f(c, SCR_IN4, ms, fms, &d_ms))) || (qe && (rc = stage_in_f(c, SCR_IN5, qe, fq, &d_qe))) || (rc = stage_out_ptr(c, SCR_OUT, out, fo, &d_out, &host)))
-        return rc;
+    const float *d_mk = call.in(SCR_IN, mk, fmk), *d_qk = call.in(SCR_IN2, qk, fq), *d_mv = call.in(SCR_IN3, mv, fmv);
+    const float *d_ms = call.in(SCR_IN4, ms, fms), *d_qe = call.in(SCR_IN5, qe, fq);                        // optional: NULL stays NULL
+    float* d_out = call.out(SCR_OUT, out, fo);
     // SCR_TOPK_IDX / SCR_TOPK_W also hold the level-1 survivors of the two-level top-k behind the final lists: [B][k][HW] + [B][S][k][HW]
     const size_t lst = (size_t)B * top_k * HW, cand = lst * (mem_topk_splits(N) > 1 ? mem_topk_splits(N) : 0);
-    if ((rc = ensure_scratch(c, SCR_SIM, (size_t)B * N * HW * 4)) || (rc = ensure_scratch(c, SCR_TOPK_IDX, (lst + cand) * 4)) ||
-        (rc = ensure_scratch(c, SCR_TOPK_W, (lst + cand) * 4))) return rc;
+    float* d_sim = (float*)call.scratch(SCR_SIM, (size_t)B * N * HW * 4);
+    int* d_idx = (int*)call.scratch(SCR_TOPK_IDX, (lst + cand) * 4);
+    float* d_w = (float*)call.scratch(SCR_TOPK_W, (lst + cand) * 4);
+    unsigned long long* d_acc = usage ? (unsigned long long*)call.scratch(SCR_USAGE_ACC, (size_t)B * N * 8) : nullptr;
+    float* d_us = call.out(SCR_SMALL, usage, (size_t)B * N * 4);
+    if (call.rc) return call.rc;
     // wave-per-query selection on a query-major similarity; beyond 16 384 memory elements the two-level kernels
     int e;
     if (mem_topk_select_supported(N)) {
-        e = launch_mem_similarity_t(d_mk, d_ms, d_qk, d_qe, (float*)c->scratch[SCR_SIM], B, CK, N, HW, c->stream);
-        if (!e) e = launch_mem_topk_select_readout((const float*)c->scratch[SCR_SIM], d_mv, (int*)c->scratch[SCR_TOPK_IDX], (float*)c->scratch[SCR_TOPK_W], (float*)d_out, B, CV, N, HW,
-                                                   top_k, c->stream);
+        e = launch_mem_similarity_t(d_mk, d_ms, d_qk, d_qe, d_sim, B, CK, N, HW, c->stream);
+        if (!e) e = launch_mem_topk_select_readout(d_sim, d_mv, d_idx, d_w, d_out, B, CV, N, HW, top_k, c->stream);
     } else {
-        e = launch_mem_similarity(d_mk, d_ms, d_qk, d_qe, (float*)c->scratch[SCR_SIM], B, CK, N, HW, c->stream);
-        if (!e) e = launch_mem_topk_readout((const float*)c->scratch[SCR_SIM], d_mv, (int*)c->scratch[SCR_TOPK_IDX], (float*)c->scratch[SCR_TOPK_W], (float*)c->scratch[SCR_TOPK_W] + lst,
-                                            (int*)c->scratch[SCR_TOPK_IDX] + lst, (float*)d_out, B, CV, N, HW, top_k, c->stream);
+        e = launch_mem_similarity(d_mk, d_ms, d_qk, d_qe, d_sim, B, CK, N, HW, c->stream);
+        if (!e) e = launch_mem_topk_readout(d_sim, d_mv, d_idx, d_w, d_w + lst, d_idx + lst, d_out, B, CV, N, HW, top_k, c->stream);
     }
-    c->stats.launches += 3;
-    if (e) return hip_fail(c, (hipError_t)e, "memory_read_topk");
-    if (usage) {                                               // row sums of the sparse affinity (do_softmax(..., return_usage=True))
-        uint8_t* d_us;
-        bool uhost;
-        if ((rc = ensure_scratch(c, SCR_USAGE_ACC, (size_t)B * N * 8)) || (rc = stage_out_ptr(c, SCR_SMALL, usage, (size_t)B * N * 4, &d_us, &uhost))) return rc;
-        e = launch_mem_usage((const int*)c->scratch[SCR_TOPK_IDX], (const float*)c->scratch[SCR_TOPK_W], (unsigned long long*)c->scratch[SCR_USAGE_ACC], (float*)d_us, B, N, HW, top_k,
-                             c->stream);
-        c->stats.launches += 2;
-        if (e) return hip_fail(c, (hipError_t)e, "memory_read_topk (usage)");
-        if ((rc = stage_out(c, usage, d_us, (size_t)B * N * 4, uhost))) return rc;
-    }
-    return stage_out(c, out, d_out, fo, host);
+    if (!call.launched(e, 3)) return call.rc;
+    if (usage) call.launched(launch_mem_usage(d_idx, d_w, d_acc, d_us, B, N, HW, top_k, c->stream), 2);   // row sums of the sparse affinity (do_softmax(..., return_usage=True))
+    return call.done();
 }
 
 int havc_memory_dense_readout(havc_ctx* c, const float* mk, const float* ms, const float* qk, const float* qe, const float* mv, float* out, int B, int CK,
                               int CV, int N, int P) {
     if (!c || !mk || !qk || !mv || !out || B < 1 || CK < 1 || CV < 1 || CV > 2048 || N < 1 || P < 1)
         return fail(c, HAVC_E_INVALID, "memory_dense_readout: bad args (CV <= 2048)");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "memory_dense_readout");
     const size_t fmk = (size_t)B * CK * N * 4, fq = (size_t)B * CK * P * 4, fms = (size_t)B * N * 4, fmv = (size_t)B * CV * N * 4, fo = (size_t)B * CV * P * 4;
-    const float *d_mk, *d_ms = nullptr, *d_qk, *d_qe = nullptr, *d_mv;
-    uint8_t* d_out;
-    bool host;
-    int rc;
-    if ((rc = stage_in_f(c, SCR_IN, mk, fmk, &d_mk)) || (rc = stage_in_f(c, SCR_IN2, qk, fq, &d_qk)) || (rc = stage_in_f(c, SCR_IN3, mv, fmv, &d_mv)) ||
-        (ms && (rc = stage_in_f(c, SCR_IN4, ms, fms, &d_ms))) || (qe && (rc = stage_in_f(c, SCR_IN5, qe, fq, &d_qe))) || (rc = stage_out_ptr(c, SCR_OUT, out, fo, &d_out, &host)) ||
-        (rc = ensure_scratch(c, SCR_SIM, (size_t)B * N * P * 4)))
-        return rc;
-    int e = launch_mem_similarity(d_mk, d_ms, d_qk, d_qe, (float*)c->scratch[SCR_SIM], B, CK, N, P, c->stream);
-    if (!e) e = launch_mem_dense_readout((const float*)c->scratch[SCR_SIM], d_mv, (float*)d_out, B, CV, N, P, c->stream);
-    c->stats.launches += 2;
-    if (e) return hip_fail(c, (hipError_t)e, "memory_dense_readout");
-    return stage_out(c, out, d_out, fo, host);
+    const float *d_mk = call.in(SCR_IN, mk, fmk), *d_qk = call.in(SCR_IN2, qk, fq), *d_mv = call.in(SCR_IN3, mv, fmv);
+    const float *d_ms = call.in(SCR_IN4, ms, fms), *d_qe = call.in(SCR_IN5, qe, fq);                        // optional: NULL stays NULL
+    float* d_out = call.out(SCR_OUT, out, fo);
+    float* d_sim = (float*)call.scratch(SCR_SIM, (size_t)B * N * P * 4);
+    if (call.rc) return call.rc;
+    int e = launch_mem_similarity(d_mk, d_ms, d_qk, d_qe, d_sim, B, CK, N, P, c->stream);
+    if (!e) e = launch_mem_dense_readout(d_sim, d_mv, d_out, B, CV, N, P, c->stream);
+    call.launched(e, 2);
+    return call.done();
 }
 
 int havc_memory_similarity(havc_ctx* c, const float* mk, const float* ms, const float* qk, const float* qe, float* sim, int B, int CK, int N, int HW) {
     if (!c || !mk || !qk || !sim || B < 1 || CK < 1 || N < 1 || HW < 1) return fail(c, HAVC_E_INVALID, "memory_similarity: bad args");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "memory_similarity");
     const size_t fmk = (size_t)B * CK * N * 4, fq = (size_t)B * CK * HW * 4, fms = (size_t)B * N * 4, fo = (size_t)B * N * HW * 4;
-    const float *d_mk, *d_ms = nullptr, *d_qk, *d_qe = nullptr;
-    uint8_t* d_out;
-    bool host;
-    int rc;
-    if ((rc = stage_in_f(c, SCR_IN, mk, fmk, &d_mk)) || (rc = stage_in_f(c, SCR_IN2, qk, fq, &d_qk)) || (ms && (rc = stage_in_f(c, SCR_IN4, ms, fms, &d_ms))) ||
-        (qe && (rc = stage_in_f(c, SCR_IN5, qe, fq, &d_qe))) || (rc = stage_out_ptr(c, SCR_OUT, sim, fo, &d_out, &host))) return rc;
-    int e = launch_mem_similarity(d_mk, d_ms, d_qk, d_qe, (float*)d_out, B, CK, N, HW, c->stream);
-    c->stats.launches++;
-    if (e) return hip_fail(c, (hipError_t)e, "memory_similarity");
-    return stage_out(c, sim, d_out, fo, host);
+    const float *d_mk = call.in(SCR_IN, mk, fmk), *d_qk = call.in(SCR_IN2, qk, fq);
+    const float *d_ms = call.in(SCR_IN4, ms, fms), *d_qe = call.in(SCR_IN5, qe, fq);                        // optional: NULL stays NULL
+    float* d_out = call.out(SCR_OUT, sim, fo);
+    if (call.rc) return call.rc;
+    call.launched(launch_mem_similarity(d_mk, d_ms, d_qk, d_qe, d_out, B, CK, N, HW, c->stream));
+    return call.done();
 }
 
 int havc_local_correlation(havc_ctx* c, const float* q, const float* k, float* out, int n, int C, int H, int W, int max_dis, int dilation, float q_scale) {
     if (!c || !q || !k || !out || n < 1 || C < 1 || H < 1 || W < 1 || max_dis < 0 || max_dis > 7 || dilation < 1)
         return fail(c, HAVC_E_INVALID, "local_correlation: bad args (max_dis 0..7, dilation >= 1)");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "local_correlation");
     const int ws = 2 * max_dis + 1;
     const size_t fi = (size_t)n * C * H * W * 4, fo = (size_t)n * ws * ws * H * W * 4;
-    const float *d_q, *d_k;
-    uint8_t* d_out;
-    bool host;
-    int rc;
-    if ((rc = stage_in_f(c, SCR_IN, q, fi, &d_q)) || (rc = stage_in_f(c, SCR_IN2, k, fi, &d_k)) || (rc = stage_out_ptr(c, SCR_OUT, out, fo, &d_out, &host))) return rc;
-    int e = launch_local_correlation(d_q, d_k, (float*)d_out, n, C, H, W, max_dis, dilation, q_scale, c->stream);
-    c->stats.launches++;
-    if (e) return hip_fail(c, (hipError_t)e, "local_correlation");
-    return stage_out(c, out, d_out, fo, host);
+    const float *d_q = call.in(SCR_IN, q, fi), *d_k = call.in(SCR_IN2, k, fi);
+    float* d_out = call.out(SCR_OUT, out, fo);
+    if (call.rc) return call.rc;
+    call.launched(launch_local_correlation(d_q, d_k, d_out, n, C, H, W, max_dis, dilation, q_scale, c->stream));
+    return call.done();
 }
 
 int havc_local_attention(havc_ctx* c, const float* q, const float* k, const float* v, const float* rel_w, const float* rel_b, float* agg, float* attn,
                          int n, int C, int CV, int H, int W, int max_dis, int dilation) {
     if (!c || !q || !k || !v || !rel_w || !rel_b || !agg || n < 1 || C < 1 || CV < 1 || H < 1 || W < 1 || max_dis < 0 || max_dis > 7 || dilation < 1)
         return fail(c, HAVC_E_INVALID, "local_attention: bad args (max_dis 0..7, dilation >= 1)");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "local_attention");
     const int ws = 2 * max_dis + 1, WW = ws * ws;
     const size_t fi = (size_t)n * C * H * W * 4, fv = (size_t)n * CV * H * W * 4, fa = (size_t)n * WW * H * W * 4, fo = (size_t)H * W * n * CV * 4;
-    const float *d_q, *d_k, *d_v, *d_rw, *d_rb;
-    uint8_t *d_agg, *d_attn;
-    bool host_agg, host_attn = false;
-    int rc;
-    if ((rc = stage_in_f(c, SCR_IN, q, fi, &d_q)) || (rc = stage_in_f(c, SCR_IN2, k, fi, &d_k)) || (rc = stage_in_f(c, SCR_IN3, v, fv, &d_v)) ||
-        (rc = stage_in_f(c, SCR_IN4, rel_w, (size_t)WW * C * 4, &d_rw)) || (rc = stage_in_f(c, SCR_IN5, rel_b, (size_t)WW * 4, &d_rb)) ||
-        (rc = stage_out_ptr(c, SCR_OUT, agg, fo, &d_agg, &host_agg))) return rc;
-    if (attn) { if ((rc = stage_out_ptr(c, SCR_SIM, attn, fa, &d_attn, &host_attn))) return rc; }
-    else { if ((rc = ensure_scratch(c, SCR_SIM, fa))) return rc; d_attn = (uint8_t*)c->scratch[SCR_SIM]; }
+    const float *d_q = call.in(SCR_IN, q, fi), *d_k = call.in(SCR_IN2, k, fi), *d_v = call.in(SCR_IN3, v, fv);
+    const float *d_rw = call.in(SCR_IN4, rel_w, (size_t)WW * C * 4), *d_rb = call.in(SCR_IN5, rel_b, (size_t)WW * 4);
+    float* d_agg = call.out(SCR_OUT, agg, fo);
+    float* d_attn = attn ? call.out(SCR_SIM, attn, fa) : (float*)call.scratch(SCR_SIM, fa);                 // a result if asked for, a workspace anyway
+    if (call.rc) return call.rc;
     // q / T with T = sqrt(d_att) = sqrt(C) (attention.py:742, 809); the relative embedding is taken from the UNSCALED q (:806)
-    int e = launch_local_correlation(d_q, d_k, (float*)d_attn, n, C, H, W, max_dis, dilation, 1.0f / sqrtf((float)C), c->stream);
-    if (!e) e = launch_local_softmax((float*)d_attn, d_q, d_rw, d_rb, n, C, H, W, max_dis, dilation, c->stream);
-    if (!e) e = launch_local_agg((const float*)d_attn, d_v, (float*)d_agg, n, CV, H, W, max_dis, dilation, c->stream);
-    c->stats.launches += 3;
-    if (e) return hip_fail(c, (hipError_t)e, "local_attention");
-    if (attn && host_attn) {
-        HIP_TRY(c, hipMemcpyAsync(attn, d_attn, fa, hipMemcpyDeviceToHost, c->stream));
-        if (!host_agg) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return stage_out(c, agg, d_agg, fo, host_agg);
+    int e = launch_local_correlation(d_q, d_k, d_attn, n, C, H, W, max_dis, dilation, 1.0f / sqrtf((float)C), c->stream);
+    if (!e) e = launch_local_softmax(d_attn, d_q, d_rw, d_rb, n, C, H, W, max_dis, dilation, c->stream);
+    if (!e) e = launch_local_agg(d_attn, d_v, d_agg, n, CV, H, W, max_dis, dilation, c->stream);
+    call.launched(e, 3);
+    return call.done();
 }
 
 // ---- ColorMNetRender's frame transforms (colormnet_render.py:285-301, 276-279) ----
 int havc_colormnet_rgb_to_lab(havc_ctx* c, const uint8_t* rgb, float* lab, int width, int height) {
     if (!c || !rgb || !lab || width < 1 || height < 1) return fail(c, HAVC_E_INVALID, "colormnet_rgb_to_lab: bad args");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "colormnet_rgb_to_lab");
     const size_t npix = (size_t)width * height;
-    const uint8_t* d_in;
-    uint8_t* d_out;
-    bool host;
-    int rc;
-    if ((rc = stage_in(c, SCR_IN, rgb, npix * 3, &d_in)) || (rc = stage_out_ptr(c, SCR_OUT, lab, npix * 12, &d_out, &host))) return rc;
-    int e = launch_cmn_rgb_to_lab(d_in, (float*)d_out, (int64_t)npix, c->stream);
-    c->stats.launches++;
-    if (e) return hip_fail(c, (hipError_t)e, "colormnet_rgb_to_lab");
-    return stage_out(c, lab, d_out, npix * 12, host);
+    const uint8_t* d_in = call.in(SCR_IN, rgb, npix * 3);
+    float* d_out = call.out(SCR_OUT, lab, npix * 12);
+    if (call.rc) return call.rc;
+    call.launched(launch_cmn_rgb_to_lab(d_in, d_out, (int64_t)npix, c->stream));
+    return call.done();
 }
 
 int havc_colormnet_lab_to_rgb(havc_ctx* c, const float* l_plane, const float* ab, uint8_t* rgb, int width, int height) {
     if (!c || !l_plane || !ab || !rgb || width < 1 || height < 1) return fail(c, HAVC_E_INVALID, "colormnet_lab_to_rgb: bad args");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "colormnet_lab_to_rgb");
     const size_t npix = (size_t)width * height;
-    const float *d_l, *d_ab;
-    uint8_t* d_out;
-    bool host;
-    int rc;
-    if ((rc = stage_in_f(c, SCR_IN, l_plane, npix * 4, &d_l)) || (rc = stage_in_f(c, SCR_IN2, ab, npix * 8, &d_ab)) || (rc = stage_out_ptr(c, SCR_OUT, rgb, npix * 3, &d_out, &host)))
-        return rc;
-    int e = launch_cmn_lab_to_rgb(d_l, d_ab, d_out, (int64_t)npix, c->stream);
-    c->stats.launches++;
-    if (e) return hip_fail(c, (hipError_t)e, "colormnet_lab_to_rgb");
-    return stage_out(c, rgb, d_out, npix * 3, host);
+    const float *d_l = call.in(SCR_IN, l_plane, npix * 4), *d_ab = call.in(SCR_IN2, ab, npix * 8);
+    uint8_t* d_out = call.out(SCR_OUT, rgb, npix * 3);
+    if (call.rc) return call.rc;
+    call.launched(launch_cmn_lab_to_rgb(d_l, d_ab, d_out, (int64_t)npix, c->stream));
+    return call.done();
 }
 
 // ---- ColorMNet: the per-frame step without tensor bookkeeping between the kernels (include/havc_mi355.h, "fast step") -----------------------
@@ -179,15 +130,11 @@ int havc_cmn_frame_in(havc_ctx* c, const uint8_t* rgb, float* lab, float* img, i
     if (!c || !rgb || !lab || width < 1 || height < 1 || padded_w < width + pad_left || padded_h < height + pad_top || pad_left < 0 || pad_top < 0 ||
         is_device_ptr(lab) == false || (img && !is_device_ptr(img)))
         return fail(c, HAVC_E_INVALID, "cmn_frame_in: bad args (lab / img are device buffers)");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
-    const uint8_t* d_in;
-    int rc;
-    if ((rc = stage_in(c, SCR_IN, rgb, (size_t)width * height * 3, &d_in))) return rc;
-    int e = launch_cmn_frame_in(d_in, lab, img, width, height, img ? padded_w : width, img ? padded_h : height, img ? pad_left : 0, img ? pad_top : 0, c->stream);
-    c->stats.launches++;
-    if (e) return hip_fail(c, (hipError_t)e, "cmn_frame_in");
-    return HAVC_OK;
+    Call call(c, "cmn_frame_in");
+    const uint8_t* d_in = call.in(SCR_IN, rgb, (size_t)width * height * 3);
+    if (call.rc) return call.rc;
+    call.launched(launch_cmn_frame_in(d_in, lab, img, width, height, img ? padded_w : width, img ? padded_h : height, img ? pad_left : 0, img ? pad_top : 0, c->stream));
+    return call.done();
 }
 
 int havc_cmn_frame_out(havc_ctx* c, const float* l_plane, const float* ab_padded, uint8_t* rgb, int width, int height, int padded_w, int padded_h,
@@ -195,17 +142,11 @@ int havc_cmn_frame_out(havc_ctx* c, const float* l_plane, const float* ab_padded
     if (!c || !l_plane || !ab_padded || !rgb || width < 1 || height < 1 || padded_w < width + pad_left || padded_h < height + pad_top || pad_left < 0 || pad_top < 0 ||
         !is_device_ptr(l_plane) || !is_device_ptr(ab_padded))
         return fail(c, HAVC_E_INVALID, "cmn_frame_out: bad args (the Lab planes are device buffers)");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
-    const size_t nb = (size_t)width * height * 3;
-    uint8_t* d_out;
-    bool host;
-    int rc;
-    if ((rc = stage_out_ptr(c, SCR_OUT, rgb, nb, &d_out, &host))) return rc;
-    int e = launch_cmn_frame_out(l_plane, ab_padded, d_out, width, height, padded_w, padded_h, pad_left, pad_top, c->stream);
-    c->stats.launches++;
-    if (e) return hip_fail(c, (hipError_t)e, "cmn_frame_out");
-    return stage_out(c, rgb, d_out, nb, host);
+    Call call(c, "cmn_frame_out");
+    uint8_t* d_out = call.out(SCR_OUT, rgb, (size_t)width * height * 3);
+    if (call.rc) return call.rc;
+    call.launched(launch_cmn_frame_out(l_plane, ab_padded, d_out, width, height, padded_w, padded_h, pad_left, pad_top, c->stream));
+    return call.done();
 }
 
 // use_count += usage, life_count += 1 from the top-k lists in SCR_BANK_IDX / SCR_BANK_W.  The accumulators (SCR_BANK_ACC) are kept at zero BETWEEN reads by the

@@ -53,18 +53,13 @@ int havc_image_luma_merge(havc_ctx* c, const uint8_t* img_dark, const uint8_t* i
 
 int havc_image_luma(havc_ctx* c, const uint8_t* img, int width, int height, double* mean_y) {
     if (!c || !img || !mean_y || width <= 0 || height <= 0) return fail(c, HAVC_E_INVALID, "image_luma: bad args");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
-    const size_t nb = (size_t)width * height * 3;
-    int rc;
-    const uint8_t* din;
-    if ((rc = stage_in(c, SCR_IN, img, nb, &din)) || (rc = ensure_scratch(c, SCR_SMALL, 256))) return rc;
-    int e = launch_luma_sum(din, (unsigned long long*)c->scratch[SCR_SMALL], (int64_t)width * height, c->stream);
-    c->stats.launches++;
-    if (e) return hip_fail(c, (hipError_t)e, "luma sum");
+    Call call(c, "image_luma");
     unsigned long long sum = 0;
-    HIP_TRY(c, hipMemcpyAsync(&sum, c->scratch[SCR_SMALL], sizeof(sum), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const uint8_t* din = call.in(SCR_IN, img, (size_t)width * height * 3);
+    void* d_sum = call.download(&sum, call.scratch(SCR_SMALL, 256), sizeof(sum));
+    if (call.rc) return call.rc;
+    call.launched(launch_luma_sum(din, (unsigned long long*)d_sum, (int64_t)width * height, c->stream));
+    if (call.done()) return call.rc;
     *mean_y = (double)sum / ((double)width * (double)height);
     return HAVC_OK;
 }
@@ -73,32 +68,27 @@ int havc_image_tweak(havc_ctx* c, const uint8_t* img, uint8_t* out, int width, i
                      float color, const double* hue_ranges, int n_ranges) {
     if (!c || !img || !out || width <= 0 || height <= 0 || n_ranges < 0 || n_ranges > HAVC_MAX_HUE_RANGES || (n_ranges && !hue_ranges))
         return fail(c, HAVC_E_INVALID, "image_tweak: bad args (at most 8 hue ranges)");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "image_tweak");
     const size_t nb = (size_t)width * height * 3;
     const int64_t npix = (int64_t)width * height;
-    int rc;
-    const uint8_t* din;
-    uint8_t* dout;
-    bool host;
-    if ((rc = stage_in(c, SCR_IN, img, nb, &din)) || (rc = stage_out_ptr(c, SCR_OUT, out, nb, &dout, &host)) || (rc = ensure_scratch(c, SCR_SMALL, 256))) return rc;
+    const uint8_t* din = call.in(SCR_IN, img, nb);
+    uint8_t* dout = call.out(SCR_OUT, out, nb);
+    unsigned long long* d_sum = (unsigned long long*)call.scratch(SCR_SMALL, 256);
+    if (call.rc) return call.rc;
     TweakArgs a{};
     a.hue_offset = hue_offset; a.brightness = brightness; a.contrast = contrast; a.color = color; a.mean_l = 0; a.n_ranges = n_ranges;
     for (int k = 0; k < n_ranges; ++k) { a.range_lo[k] = hue_ranges[2 * k]; a.range_hi[k] = hue_ranges[2 * k + 1]; }
     if (contrast != 1.f) {
         // ImageEnhance.Contrast: degenerate = solid int(mean(L) + 0.5) of the image as it enters the step
-        int e = launch_image_tweak(din, dout, npix, a, (unsigned long long*)c->scratch[SCR_SMALL], true, c->stream);
-        c->stats.launches++;
-        if (e) return hip_fail(c, (hipError_t)e, "image_tweak (L sum)");
         unsigned long long sum = 0;
-        HIP_TRY(c, hipMemcpyAsync(&sum, c->scratch[SCR_SMALL], sizeof(sum), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        call.launched(launch_image_tweak(din, dout, npix, a, d_sum, true, c->stream));
+        call.copy(&sum, d_sum, sizeof(sum), hipMemcpyDeviceToHost);
+        call.sync();
+        if (call.rc) return call.rc;
         a.mean_l = (int)((double)sum / (double)npix + 0.5);
     }
-    int e = launch_image_tweak(din, dout, npix, a, (unsigned long long*)c->scratch[SCR_SMALL], false, c->stream);
-    c->stats.launches++;
-    if (e) return hip_fail(c, (hipError_t)e, "image_tweak");
-    return stage_out(c, out, dout, nb, host);
+    call.launched(launch_image_tweak(din, dout, npix, a, d_sum, false, c->stream));
+    return call.done();
 }
 
 // the argument normalisation of np_image_chroma_tweak (restcolor.py:288-350): clamps, half-degree hue steps, which sub-steps run
@@ -171,29 +161,22 @@ static TileArgs tile_args(const havc_tile_geom* g) {
     a.base_w = g->base_w; a.base_h = g->base_h; a.ox = g->overlap_x; a.oy = g->overlap_y; a.mask_val = g->mask_val;
     return a;
 }
-static size_t tile_stage_bytes(size_t n) { return (n + 255) & ~(size_t)255; }
 
 int havc_tile_slice(havc_ctx* c, const uint8_t* clip, uint8_t* const* tiles, const havc_tile_geom* g) {
     if (!c || !clip || !tiles) return fail(c, HAVC_E_INVALID, "tile_slice: bad args");
     if (const char* why = tile_geom_error(g)) return fail(c, HAVC_E_INVALID, (std::string("tile_slice: ") + why).c_str());
     for (int t = 0; t < g->n_tiles; ++t) if (!tiles[t]) return fail(c, HAVC_E_INVALID, "tile_slice: NULL tile");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "tile_slice");
     TileArgs a = tile_args(g);
     const size_t cb = (size_t)a.n * a.h * a.w * 3, tb = (size_t)a.n * (a.base_h + a.oy) * (a.base_w + a.ox) * 3;
-    int rc, n_host = 0;
-    bool host[4] = {false, false, false, false};
-    for (int t = 0; t < a.n_tiles; ++t) n_host += (host[t] = !is_device_ptr(tiles[t]));
-    const uint8_t* d_clip;
-    if ((rc = stage_in(c, SCR_IN, clip, cb, &d_clip)) || (n_host && (rc = ensure_scratch(c, SCR_OUT, tile_stage_bytes(tb) * n_host)))) return rc;
-    for (int t = 0, k = 0; t < a.n_tiles; ++t) a.tile[t] = host[t] ? (uint8_t*)c->scratch[SCR_OUT] + tile_stage_bytes(tb) * k++ : tiles[t];
-    const int e = launch_tile_slice(d_clip, a, c->stream);
-    c->stats.launches++;
-    if (e) return hip_fail(c, (hipError_t)e, "tile_slice");
-    for (int t = 0; t < a.n_tiles; ++t)
-        if (host[t]) HIP_TRY(c, hipMemcpyAsync(tiles[t], a.tile[t], tb, hipMemcpyDeviceToHost, c->stream));
-    if (n_host) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return HAVC_OK;
+    const uint8_t* d_clip = call.in(SCR_IN, clip, cb);
+    Call::Pack host_tiles(SCR_OUT);
+    for (int t = 0; t < a.n_tiles; ++t) call.add(host_tiles, tiles[t], tb);
+    call.reserve(host_tiles);
+    for (int t = 0; t < a.n_tiles; ++t) a.tile[t] = call.out(host_tiles, tiles[t], tb);
+    if (call.rc) return call.rc;
+    call.launched(launch_tile_slice(d_clip, a, c->stream));
+    return call.done();
 }
 
 int havc_tile_reconstruct(havc_ctx* c, const uint8_t* const* tiles, const uint8_t* clip_orig, uint8_t* out, const havc_tile_geom* g) {
@@ -203,38 +186,20 @@ int havc_tile_reconstruct(havc_ctx* c, const uint8_t* const* tiles, const uint8_
     for (int t = 0; t < g->n_tiles; ++t)
         if (!tiles[t] || tiles[t] == out) return fail(c, HAVC_E_INVALID, "tile_reconstruct: NULL tile, or out is a tile");
     if (g->recover_luma && clip_orig == out) return fail(c, HAVC_E_INVALID, "tile_reconstruct: out must not be clip_orig");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "tile_reconstruct");
     TileArgs a = tile_args(g);
     const size_t cb = (size_t)a.n * a.h * a.w * 3, tb = (size_t)a.n * (a.base_h + a.oy) * (a.base_w + a.ox) * 3;
     const uint8_t* orig = g->recover_luma ? clip_orig : nullptr;
-    // host operands share one staging buffer (SCR_IN), sized before the first copy into it
-    size_t need = 0;
-    for (int t = 0; t < a.n_tiles; ++t) if (!is_device_ptr(tiles[t])) need += tile_stage_bytes(tb);
-    if (orig && !is_device_ptr(orig)) need += tile_stage_bytes(cb);
-    int rc;
-    uint8_t* dout;
-    bool host_out;
-    if ((need && (rc = ensure_scratch(c, SCR_IN, need))) || (rc = stage_out_ptr(c, SCR_OUT, out, cb, &dout, &host_out))) return rc;
-    size_t at = 0;
-    auto staged = [&](const uint8_t* p, size_t nb, const uint8_t** d) -> int {
-        if (is_device_ptr(p)) { *d = p; return HAVC_OK; }
-        uint8_t* dst = (uint8_t*)c->scratch[SCR_IN] + at;
-        at += tile_stage_bytes(nb);
-        HIP_TRY(c, hipMemcpyAsync(dst, p, nb, hipMemcpyHostToDevice, c->stream));
-        *d = dst;
-        return HAVC_OK;
-    };
-    for (int t = 0; t < a.n_tiles; ++t) {
-        const uint8_t* d;
-        if ((rc = staged(tiles[t], tb, &d))) return rc;
-        a.tile[t] = const_cast<uint8_t*>(d);
-    }
-    if (orig && (rc = staged(orig, cb, &orig))) return rc;
-    const int e = launch_tile_reconstruct(a, orig, dout, c->stream);
-    c->stats.launches++;
-    if (e) return hip_fail(c, (hipError_t)e, "tile_reconstruct");
-    return stage_out(c, out, dout, cb, host_out);
+    Call::Pack inputs(SCR_IN);                                           // the host tiles and a host clip_orig share one staging buffer
+    for (int t = 0; t < a.n_tiles; ++t) call.add(inputs, tiles[t], tb);
+    if (orig) call.add(inputs, orig, cb);
+    call.reserve(inputs);
+    uint8_t* dout = call.out(SCR_OUT, out, cb);
+    for (int t = 0; t < a.n_tiles; ++t) a.tile[t] = const_cast<uint8_t*>(call.in(inputs, tiles[t], tb));
+    if (orig) orig = call.in(inputs, orig, cb);
+    if (call.rc) return call.rc;
+    call.launched(launch_tile_reconstruct(a, orig, dout, c->stream));
+    return call.done();
 }
 
 // ---- HAVC_SceneDetect's per-frame statistics (scdetect.hip) ----
@@ -242,33 +207,34 @@ static_assert(sizeof(SceneRec) == sizeof(havc_scene_rec) && sizeof(havc_scene_re
 
 int havc_scene_norm_value(int k, int d) { return scene_norm_value(k, d); }
 
+// what scdetect.hip and scedge.hip ask of the integer luma coefficients: the 16.16 sum stays a byte
+static int luma_coef_check(havc_ctx* c, const char* what, int cr, int cg, int cb, int bias) {
+    if (cr < 0 || cg < 0 || cb < 0 || bias < 0 || ((int64_t)cr + cg + cb) * 255 + bias >= ((int64_t)256 << 16))
+        return fail(c, HAVC_E_INVALID, std::string(what) + ": luma coefficients must be >= 0 and keep Y = (cr*R + cg*G + cb*B + bias) >> 16 below 256");
+    return HAVC_OK;
+}
+
 int havc_scene_stats(havc_ctx* c, const uint8_t* clip, const havc_scene_params* p, havc_scene_rec* out) {
     if (!c || !clip || !p || !out) return fail(c, HAVC_E_INVALID, "scene_stats: bad args");
     if (p->width <= 0 || p->height <= 0 || p->n_frames <= 0 || (int64_t)p->width * p->height > ((int64_t)1 << 31))
         return fail(c, HAVC_E_INVALID, "scene_stats: bad clip size (at most 2^31 pixels per frame)");
     if (p->offset < 1 || p->offset > 25) return fail(c, HAVC_E_INVALID, "scene_stats: offset must be 1..25");
-    if (p->cr < 0 || p->cg < 0 || p->cb < 0 || p->bias < 0 || ((int64_t)p->cr + p->cg + p->cb) * 255 + p->bias >= ((int64_t)256 << 16))
-        return fail(c, HAVC_E_INVALID, "scene_stats: luma coefficients must be >= 0 and keep Y = (cr*R + cg*G + cb*B + bias) >> 16 below 256");
+    if (int rc = luma_coef_check(c, "scene_stats", p->cr, p->cg, p->cb, p->bias)) return rc;
     if (p->normalize && !(p->tht_black >= 0.0 && p->tht_white <= 1.0 && p->tht_black <= p->tht_white))
         return fail(c, HAVC_E_INVALID, "scene_stats: normalize needs 0 <= tht_black <= tht_white <= 1");
     if (is_device_ptr(out)) return fail(c, HAVC_E_INVALID, "scene_stats: the records are downloaded: out must be host memory");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "scene_stats");
     SceneStatsArgs a{};
     a.n = p->n_frames; a.h = p->height; a.w = p->width; a.offset = p->offset;
     a.cr = p->cr; a.cg = p->cg; a.cb = p->cb; a.bias = p->bias;
     a.normalize = p->normalize != 0; a.tht_black = p->tht_black; a.tht_white = p->tht_white;
     const size_t cb = (size_t)a.n * a.h * a.w * 3, rb = (size_t)a.n * sizeof(SceneRec);
-    int rc;
-    const uint8_t* d_clip;
-    if ((rc = stage_in(c, SCR_IN, clip, cb, &d_clip)) || (rc = ensure_scratch(c, SCR_SMALL, rb))) return rc;
-    SceneRec* d_rec = (SceneRec*)c->scratch[SCR_SMALL];
-    HIP_TRY(c, hipMemsetAsync(d_rec, 0, rb, c->stream));
-    const int e = launch_scene_stats(d_clip, d_rec, a, c->stream);
-    c->stats.launches += a.normalize ? 2 : 1;
-    if (e) return hip_fail(c, (hipError_t)e, "scene_stats");
-    HIP_TRY(c, hipMemcpyAsync(out, d_rec, rb, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const uint8_t* d_clip = call.in(SCR_IN, clip, cb);
+    SceneRec* d_rec = (SceneRec*)call.download(out, call.scratch(SCR_SMALL, rb), rb);
+    if (call.rc) return call.rc;
+    call.zero(d_rec, rb);
+    call.launched(launch_scene_stats(d_clip, d_rec, a, c->stream), a.normalize ? 2 : 1);
+    if (call.done()) return call.rc;
     for (int i = 0; i < a.n; ++i) out[i].min_y = 255 - out[i].min_y;       // kept as 255 - min on the device (scdetect.hip)
     return HAVC_OK;
 }
@@ -294,19 +260,15 @@ int havc_scene_hist(havc_ctx* c, const uint8_t* clip, int n_frames, int width, i
     if (rc) return rc;
     for (int i = 0; i < k; ++i)
         if (idx[i] < 0 || idx[i] >= n_frames) return fail(c, HAVC_E_INVALID, "scene_hist: a frame number is outside the clip");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "scene_hist");
     const size_t cb = (size_t)n_frames * height * width * 3, ib = (size_t)k * sizeof(int), ob = (size_t)k * 256 * sizeof(uint32_t);
-    const uint8_t* d_clip;
-    if ((rc = stage_in(c, SCR_IN, clip, cb, &d_clip)) || (rc = ensure_scratch(c, SCR_IN2, ib)) || (rc = ensure_scratch(c, SCR_SMALL, ob))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->scratch[SCR_IN2], idx, ib, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->scratch[SCR_SMALL], 0, ob, c->stream));
-    const int e = launch_scene_hist(d_clip, (const int*)c->scratch[SCR_IN2], k, (unsigned*)c->scratch[SCR_SMALL], height, width, c->stream);
-    c->stats.launches++;
-    if (e) return hip_fail(c, (hipError_t)e, "scene_hist");
-    HIP_TRY(c, hipMemcpyAsync(out, c->scratch[SCR_SMALL], ob, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return HAVC_OK;
+    const uint8_t* d_clip = call.in(SCR_IN, clip, cb);
+    const int* d_idx = call.in(SCR_IN2, idx, ib);
+    unsigned* d_hist = (unsigned*)call.download(out, call.scratch(SCR_SMALL, ob), ob);
+    if (call.rc) return call.rc;
+    call.zero(d_hist, ob);
+    call.launched(launch_scene_hist(d_clip, d_idx, k, d_hist, height, width, c->stream));
+    return call.done();
 }
 
 int havc_scene_ssim(havc_ctx* c, const uint8_t* clip, int n_frames, int width, int height, const int* pairs, int m, double* out) {
@@ -317,19 +279,14 @@ int havc_scene_ssim(havc_ctx* c, const uint8_t* clip, int n_frames, int width, i
         if (pairs[i] < 0 || pairs[i] >= n_frames) return fail(c, HAVC_E_INVALID, "scene_ssim: a frame number is outside the clip");
     const int64_t tiles = scene_ssim_tiles(height, width);
     if ((int64_t)m * tiles > 0x7FFFFFFFll) return fail(c, HAVC_E_INVALID, "scene_ssim: too many pairs for one launch at this size");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "scene_ssim");
     const size_t cb = (size_t)n_frames * height * width * 3, pb = (size_t)m * 2 * sizeof(int), ob = (size_t)m * sizeof(double);
-    const uint8_t* d_clip;
-    if ((rc = stage_in(c, SCR_IN, clip, cb, &d_clip)) || (rc = ensure_scratch(c, SCR_IN2, pb)) || (rc = ensure_scratch(c, SCR_SMALL, ob * (size_t)(1 + tiles)))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->scratch[SCR_IN2], pairs, pb, hipMemcpyHostToDevice, c->stream));
-    double* d_out = (double*)c->scratch[SCR_SMALL];                          // m results, then m * tiles partials
-    const int e = launch_scene_ssim(d_clip, (const int*)c->scratch[SCR_IN2], m, d_out + m, d_out, height, width, c->stream);
-    c->stats.launches += 2;
-    if (e) return hip_fail(c, (hipError_t)e, "scene_ssim");
-    HIP_TRY(c, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return HAVC_OK;
+    const uint8_t* d_clip = call.in(SCR_IN, clip, cb);
+    const int* d_pairs = call.in(SCR_IN2, pairs, pb);
+    double* d_out = (double*)call.download(out, call.scratch(SCR_SMALL, ob * (size_t)(1 + tiles)), ob);      // m results, then m * tiles partials
+    if (call.rc) return call.rc;
+    call.launched(launch_scene_ssim(d_clip, d_pairs, m, d_out + m, d_out, height, width, c->stream), 2);
+    return call.done();
 }
 
 // ---- HAVC_SceneDetectEdges' per-frame statistics (scedge.hip) ----
@@ -351,12 +308,10 @@ int havc_scene_edge_stats(havc_ctx* c, const uint8_t* clip, const havc_edge_para
         return fail(c, HAVC_E_INVALID, "scene_edge_stats: bad clip size (at most 16384 x 16384)");
     if (p->offset < 1 || p->offset > 25) return fail(c, HAVC_E_INVALID, "scene_edge_stats: offset must be 1..25");
     if (p->offset >= p->n_frames) return fail(c, HAVC_E_INVALID, "scene_edge_stats: offset must be smaller than the number of frames");
-    if (p->cr < 0 || p->cg < 0 || p->cb < 0 || p->bias < 0 || ((int64_t)p->cr + p->cg + p->cb) * 255 + p->bias >= ((int64_t)256 << 16))
-        return fail(c, HAVC_E_INVALID, "scene_edge_stats: luma coefficients must be >= 0 and keep Y = (cr*R + cg*G + cb*B + bias) >> 16 below 256");
+    if (int rc = luma_coef_check(c, "scene_edge_stats", p->cr, p->cg, p->cb, p->bias)) return rc;
     if (!(p->sigma > 0.0 && p->sigma <= 2.5)) return fail(c, HAVC_E_INVALID, "scene_edge_stats: sigma must be in (0, 2.5]");
     if (is_device_ptr(out)) return fail(c, HAVC_E_INVALID, "scene_edge_stats: the records are downloaded: out must be host memory");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "scene_edge_stats");
     EdgeStatsArgs a{};
     a.n = p->n_frames; a.h = p->height; a.w = p->width; a.offset = p->offset;
     a.cr = p->cr; a.cg = p->cg; a.cb = p->cb; a.bias = p->bias;
@@ -364,21 +319,13 @@ int havc_scene_edge_stats(havc_ctx* c, const uint8_t* clip, const havc_edge_para
     edge_weights(p->sigma, a.radius, a.wt);
     edge_enhance_table(a.enh);
     const size_t pb = (size_t)a.n * a.h * a.w, cb = pb * 3, rb = (size_t)a.n * sizeof(EdgeRec);
-    int rc;
-    const uint8_t* d_clip;
-    uint8_t* d_tap = nullptr;
-    bool host_tap = false;
-    if ((rc = stage_in(c, SCR_IN, clip, cb, &d_clip)) || (rc = ensure_scratch(c, SCR_SMALL, rb)) ||
-        (mask_tap && (rc = stage_out_ptr(c, SCR_OUT, mask_tap, pb, &d_tap, &host_tap)))) return rc;
-    EdgeRec* d_rec = (EdgeRec*)c->scratch[SCR_SMALL];
-    HIP_TRY(c, hipMemsetAsync(d_rec, 0, rb, c->stream));
-    const int e = launch_scene_edge_stats(d_clip, d_rec, d_tap, a, c->stream);
-    c->stats.launches++;
-    if (e) return hip_fail(c, (hipError_t)e, "scene_edge_stats");
-    HIP_TRY(c, hipMemcpyAsync(out, d_rec, rb, hipMemcpyDeviceToHost, c->stream));
-    if (mask_tap && (rc = stage_out(c, mask_tap, d_tap, pb, host_tap))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return HAVC_OK;
+    const uint8_t* d_clip = call.in(SCR_IN, clip, cb);
+    EdgeRec* d_rec = (EdgeRec*)call.download(out, call.scratch(SCR_SMALL, rb), rb);
+    uint8_t* d_tap = call.out(SCR_OUT, mask_tap, pb);                    // NULL without a tap
+    if (call.rc) return call.rc;
+    call.zero(d_rec, rb);
+    call.launched(launch_scene_edge_stats(d_clip, d_rec, d_tap, a, c->stream));
+    return call.done();
 }
 
 // ---- HAVC_bw_tune / HAVC_auto_levels: rgb_balance + rgb_equalizer on a clip (equalize.hip) ----
@@ -413,8 +360,7 @@ int havc_equalize_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const havc
     if (!(p->clip_limit >= 0.0 && p->clip_limit <= 1e6)) return fail(c, HAVC_E_INVALID, "equalize_clip: clip_limit must be in [0, 1e6]");
     for (int k = 0; k < 3; ++k)
         if (p->balance && !(p->rgb_factor[k] >= 0.0 && p->rgb_factor[k] <= 16.0)) return fail(c, HAVC_E_INVALID, "equalize_clip: rgb_factor must be in [0, 16]");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "equalize_clip");
     EqArgs a{};
     a.n = p->n_frames; a.h = p->height; a.w = p->width; a.method = p->method;
     a.luma_blend = p->luma_blend != 0; a.range_tv = p->range_tv != 0; a.balance = p->balance != 0;
@@ -424,16 +370,13 @@ int havc_equalize_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const havc
     memcpy(a.lut_in, p->lut_in, 256);
     memcpy(a.lut_out, p->lut_out, 256);
     const size_t cb = (size_t)a.n * a.h * a.w * 3, wb = equalize_workspace_bytes(a.n, a.method);
-    int rc;
-    const uint8_t* d_src;
-    uint8_t* d_dst;
-    bool host;
-    if ((rc = stage_in(c, SCR_IN, src, cb, &d_src)) || (rc = stage_out_ptr(c, SCR_OUT, dst, cb, &d_dst, &host)) || (rc = ensure_scratch(c, SCR_SMALL, wb))) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->scratch[SCR_SMALL], 0, (size_t)a.n * (sizeof(EqFrameRec) + 3 * 256 * sizeof(unsigned)), c->stream));
-    const int e = launch_equalize(d_src, d_dst, c->scratch[SCR_SMALL], a, c->stream);
-    c->stats.launches += a.balance ? 3 : 2;
-    if (e) return hip_fail(c, (hipError_t)e, "equalize_clip");
-    return stage_out(c, dst, d_dst, cb, host);
+    const uint8_t* d_src = call.in(SCR_IN, src, cb);
+    uint8_t* d_dst = call.out(SCR_OUT, dst, cb);
+    void* d_ws = call.scratch(SCR_SMALL, wb);
+    if (call.rc) return call.rc;
+    call.zero(d_ws, (size_t)a.n * (sizeof(EqFrameRec) + 3 * 256 * sizeof(unsigned)));
+    call.launched(launch_equalize(d_src, d_dst, d_ws, a, c->stream), a.balance ? 3 : 2);
+    return call.done();
 }
 
 // ---- HAVC_retinex: multi-scale Retinex (MSRCP) on a clip, chunk by chunk (retinex.hip) ----
@@ -476,8 +419,7 @@ int havc_retinex_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const havc_
         if (!(p->sigma[k] >= 0.5 && p->sigma[k] <= 10000.0)) return fail(c, HAVC_E_INVALID, "retinex_clip: every sigma must be in [0.5, 10000]");
     if (!(p->luma_dark == p->luma_dark) || !(p->luma_bright == p->luma_bright)) return fail(c, HAVC_E_INVALID, "retinex_clip: luma_dark / luma_bright is NaN");
     if (p->chunk_frames < 0) return fail(c, HAVC_E_INVALID, "retinex_clip: chunk_frames must be >= 0");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "retinex_clip");
     RetArgs a{};
     a.h = p->height; a.w = p->width; a.ns = p->n_sigmas;
     a.sF = p->fulls ? 0 : 16; a.sR = p->fulls ? 255 : 219;
@@ -487,30 +429,25 @@ int havc_retinex_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const havc_
     for (int k = 0; k < a.ns; ++k) ret_coefficients(p->sigma[k], a.coef[k]);
     const int chunk = retinex_chunk_frames(p);
     const size_t npix = (size_t)a.h * a.w, fb = npix * 3, cb = (size_t)p->n_frames * fb, pb = npix * sizeof(double);
-    int rc;
-    const uint8_t* d_src;
-    uint8_t* d_dst;
-    bool host;
-    if ((rc = stage_in(c, SCR_IN, src, cb, &d_src)) || (rc = stage_out_ptr(c, SCR_OUT, dst, cb, &d_dst, &host)) ||
-        (rc = ensure_scratch(c, SCR_SMALL, retinex_record_bytes(chunk))) || (rc = ensure_scratch(c, SCR_RETINEX_PLANES, (size_t)chunk * a.ns * pb)) ||
-        (tap && (rc = ensure_scratch(c, SCR_RETINEX_TAP, (size_t)chunk * (a.ns + 1) * pb)))) return rc;
-    double* d_planes = (double*)c->scratch[SCR_RETINEX_PLANES];
-    double* d_tap_g = tap ? (double*)c->scratch[SCR_RETINEX_TAP] : nullptr;
+    const uint8_t* d_src = call.in(SCR_IN, src, cb);
+    uint8_t* d_dst = call.out(SCR_OUT, dst, cb);
+    void* d_rec = call.scratch(SCR_SMALL, retinex_record_bytes(chunk));
+    double* d_planes = (double*)call.scratch(SCR_RETINEX_PLANES, (size_t)chunk * a.ns * pb);
+    double* d_tap_g = tap ? (double*)call.scratch(SCR_RETINEX_TAP, (size_t)chunk * (a.ns + 1) * pb) : nullptr;
+    if (call.rc) return call.rc;
     double* d_tap_p = tap ? d_tap_g + (size_t)chunk * a.ns * npix : nullptr;
+    const hipMemcpyKind tap_kind = is_device_ptr(tap) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     for (int f0 = 0; f0 < p->n_frames; f0 += chunk) {
         a.n = std::min(chunk, p->n_frames - f0);
-        HIP_TRY(c, hipMemsetAsync(c->scratch[SCR_SMALL], 0, retinex_record_bytes(a.n), c->stream));
-        const int e = launch_retinex(d_src + (size_t)f0 * fb, d_dst + (size_t)f0 * fb, d_planes, c->scratch[SCR_SMALL], d_tap_g, d_tap_p, a, c->stream);
-        c->stats.launches += 7;
-        if (e) return hip_fail(c, (hipError_t)e, "retinex_clip");
-        for (int f = 0; tap && f < a.n; ++f) {                   // per frame: the n_sigmas Gaussian planes, then the product plane
+        call.zero(d_rec, retinex_record_bytes(a.n));
+        if (!call.launched(launch_retinex(d_src + (size_t)f0 * fb, d_dst + (size_t)f0 * fb, d_planes, d_rec, d_tap_g, d_tap_p, a, c->stream), 7)) return call.rc;
+        for (int f = 0; tap && f < a.n; ++f) {                   // per frame: the n_sigmas Gaussian planes, then the product plane; the next chunk reuses the slot
             double* t = tap + (size_t)(f0 + f) * (a.ns + 1) * npix;
-            HIP_TRY(c, hipMemcpyAsync(t, d_tap_g + (size_t)f * a.ns * npix, a.ns * pb, hipMemcpyDefault, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(t + (size_t)a.ns * npix, d_tap_p + (size_t)f * npix, pb, hipMemcpyDefault, c->stream));
+            call.copy(t, d_tap_g + (size_t)f * a.ns * npix, a.ns * pb, tap_kind);
+            call.copy(t + (size_t)a.ns * npix, d_tap_p + (size_t)f * npix, pb, tap_kind);
         }
     }
-    if (tap && !is_device_ptr(tap)) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return stage_out(c, dst, d_dst, cb, host);
+    return call.done();
 }
 
 // ---- HAVC_tweak: RGB24 -> YUV420P8 -> RGB24 with vs_tweak's steps in between, and HAVC_adjust_rgb as per-frame tables (tweak.hip) ----
@@ -540,74 +477,50 @@ static int tweak_chunk_frames(int width, int height, int n_frames, int want) {
     return (int)k;
 }
 
-// a plane set that is partly in host memory: device planes are used in place, host planes get room in SCR_TWEAK_YUV
-struct TweakPlanes { uint8_t* d[3]; bool host[3]; size_t bytes[3]; };
-static int tweak_stage_planes(havc_ctx* c, uint8_t* const p[3], int width, int height, int n_frames, bool upload, TweakPlanes* out) {
-    const size_t pb = (size_t)n_frames * width * height;
-    out->bytes[0] = pb; out->bytes[1] = out->bytes[2] = pb / 4;
-    size_t need = 0;
-    for (int k = 0; k < 3; ++k) { out->host[k] = !is_device_ptr(p[k]); if (out->host[k]) need += out->bytes[k]; }
-    int rc;
-    if (need && (rc = ensure_scratch(c, SCR_TWEAK_YUV, need))) return rc;
-    size_t off = 0;
-    for (int k = 0; k < 3; ++k) {
-        if (!out->host[k]) { out->d[k] = p[k]; continue; }
-        out->d[k] = (uint8_t*)c->scratch[SCR_TWEAK_YUV] + off;
-        off += out->bytes[k];
-        if (upload) HIP_TRY(c, hipMemcpyAsync(out->d[k], p[k], out->bytes[k], hipMemcpyHostToDevice, c->stream));
-    }
-    return HAVC_OK;
-}
-
 int havc_rgb_to_yuv420(havc_ctx* c, const uint8_t* src, uint8_t* y, uint8_t* u, uint8_t* v, int width, int height, int n_frames) {
     if (!c || !src || !y || !u || !v) return fail(c, HAVC_E_INVALID, "rgb_to_yuv420: bad args");
     int rc = tweak_size_check(c, "rgb_to_yuv420", width, height, n_frames);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "rgb_to_yuv420");
     const size_t pb = (size_t)width * height, qb = pb / 4;
-    const uint8_t* d_src;
-    uint8_t* const planes[3] = {y, u, v};
-    TweakPlanes tp;
-    if ((rc = stage_in(c, SCR_IN, src, (size_t)n_frames * pb * 3, &d_src)) || (rc = tweak_stage_planes(c, planes, width, height, n_frames, false, &tp))) return rc;
+    const uint8_t* d_src = call.in(SCR_IN, src, (size_t)n_frames * pb * 3);
+    Call::Pack planes(SCR_TWEAK_YUV);                                    // the host planes among y, u, v
+    call.add(planes, y, n_frames * pb); call.add(planes, u, n_frames * qb); call.add(planes, v, n_frames * qb);
+    call.reserve(planes);
+    uint8_t *d_y = call.out(planes, y, n_frames * pb), *d_u = call.out(planes, u, n_frames * qb), *d_v = call.out(planes, v, n_frames * qb);
+    if (call.rc) return call.rc;
     TweakFwdArgs a{};
     a.h = height; a.w = width;
     const int chunk = tweak_chunk_frames(width, height, n_frames, 0);
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
         a.n = std::min(chunk, n_frames - f0);
-        const int e = launch_tweak_forward(d_src + (size_t)f0 * pb * 3, tp.d[0] + (size_t)f0 * pb, tp.d[1] + (size_t)f0 * qb, tp.d[2] + (size_t)f0 * qb, a, c->stream);
-        c->stats.launches++;
-        if (e) return hip_fail(c, (hipError_t)e, "rgb_to_yuv420");
+        const int e = launch_tweak_forward(d_src + (size_t)f0 * pb * 3, d_y + (size_t)f0 * pb, d_u + (size_t)f0 * qb, d_v + (size_t)f0 * qb, a, c->stream);
+        if (!call.launched(e)) return call.rc;
     }
-    bool any_host = false;
-    for (int k = 0; k < 3; ++k)
-        if (tp.host[k]) { any_host = true; HIP_TRY(c, hipMemcpyAsync(planes[k], tp.d[k], tp.bytes[k], hipMemcpyDeviceToHost, c->stream)); }
-    if (any_host) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return HAVC_OK;
+    return call.done();
 }
 
 int havc_yuv420_to_rgb(havc_ctx* c, const uint8_t* y, const uint8_t* u, const uint8_t* v, uint8_t* dst, int width, int height, int n_frames) {
     if (!c || !y || !u || !v || !dst) return fail(c, HAVC_E_INVALID, "yuv420_to_rgb: bad args");
     int rc = tweak_size_check(c, "yuv420_to_rgb", width, height, n_frames);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "yuv420_to_rgb");
     const size_t pb = (size_t)width * height, qb = pb / 4, cb = (size_t)n_frames * pb * 3;
-    uint8_t* const planes[3] = {const_cast<uint8_t*>(y), const_cast<uint8_t*>(u), const_cast<uint8_t*>(v)};
-    TweakPlanes tp;
-    uint8_t* d_dst;
-    bool host;
-    if ((rc = tweak_stage_planes(c, planes, width, height, n_frames, true, &tp)) || (rc = stage_out_ptr(c, SCR_OUT, dst, cb, &d_dst, &host))) return rc;
+    Call::Pack planes(SCR_TWEAK_YUV);                                    // the host planes among y, u, v
+    call.add(planes, y, n_frames * pb); call.add(planes, u, n_frames * qb); call.add(planes, v, n_frames * qb);
+    call.reserve(planes);
+    const uint8_t *d_y = call.in(planes, y, n_frames * pb), *d_u = call.in(planes, u, n_frames * qb), *d_v = call.in(planes, v, n_frames * qb);
+    uint8_t* d_dst = call.out(SCR_OUT, dst, cb);
+    if (call.rc) return call.rc;
     TweakBackArgs a{};
     a.h = height; a.w = width;
     const int chunk = tweak_chunk_frames(width, height, n_frames, 0);
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
         a.n = std::min(chunk, n_frames - f0);
-        const int e = launch_tweak_back(tp.d[0] + (size_t)f0 * pb, tp.d[1] + (size_t)f0 * qb, tp.d[2] + (size_t)f0 * qb, d_dst + (size_t)f0 * pb * 3, a, c->stream);
-        c->stats.launches++;
-        if (e) return hip_fail(c, (hipError_t)e, "yuv420_to_rgb");
+        const int e = launch_tweak_back(d_y + (size_t)f0 * pb, d_u + (size_t)f0 * qb, d_v + (size_t)f0 * qb, d_dst + (size_t)f0 * pb * 3, a, c->stream);
+        if (!call.launched(e)) return call.rc;
     }
-    return stage_out(c, dst, d_dst, cb, host);
+    return call.done();
 }
 
 int havc_tweak_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const havc_tweak_params* p) {
@@ -616,8 +529,7 @@ int havc_tweak_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const havc_tw
     if (rc) return rc;
     if (p->chunk_frames < 0) return fail(c, HAVC_E_INVALID, "tweak_clip: chunk_frames must be >= 0");
     if (p->has_hue_sat && !(std::isfinite(p->hue_c) && std::isfinite(p->hue_s))) return fail(c, HAVC_E_INVALID, "tweak_clip: hue_c / hue_s must be finite");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "tweak_clip");
     TweakFwdArgs fa{};
     fa.h = p->height; fa.w = p->width;
     fa.has_gamma = p->has_gamma != 0; fa.has_hue_sat = p->has_hue_sat != 0; fa.has_luma = p->has_luma != 0;
@@ -628,22 +540,19 @@ int havc_tweak_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const havc_tw
     ba.h = p->height; ba.w = p->width;
     const int chunk = tweak_chunk_frames(p->width, p->height, p->n_frames, p->chunk_frames);
     const size_t pb = (size_t)p->width * p->height, qb = pb / 4, fb = pb * 3, cb = (size_t)p->n_frames * fb;
-    const uint8_t* d_src;
-    uint8_t* d_dst;
-    bool host;
-    if ((rc = stage_in(c, SCR_IN, src, cb, &d_src)) || (rc = stage_out_ptr(c, SCR_OUT, dst, cb, &d_dst, &host)) ||
-        (rc = ensure_scratch(c, SCR_TWEAK_YUV, (size_t)chunk * (pb + 2 * qb)))) return rc;
-    uint8_t* d_y = (uint8_t*)c->scratch[SCR_TWEAK_YUV];
+    const uint8_t* d_src = call.in(SCR_IN, src, cb);
+    uint8_t* d_dst = call.out(SCR_OUT, dst, cb);
+    uint8_t* d_y = (uint8_t*)call.scratch(SCR_TWEAK_YUV, (size_t)chunk * (pb + 2 * qb));
+    if (call.rc) return call.rc;
     uint8_t* d_u = d_y + (size_t)chunk * pb;
     uint8_t* d_v = d_u + (size_t)chunk * qb;
     for (int f0 = 0; f0 < p->n_frames; f0 += chunk) {
         fa.n = ba.n = std::min(chunk, p->n_frames - f0);
         int e = launch_tweak_forward(d_src + (size_t)f0 * fb, d_y, d_u, d_v, fa, c->stream);
         if (!e) e = launch_tweak_back(d_y, d_u, d_v, d_dst + (size_t)f0 * fb, ba, c->stream);
-        c->stats.launches += 2;
-        if (e) return hip_fail(c, (hipError_t)e, "tweak_clip");
+        if (!call.launched(e, 2)) return call.rc;
     }
-    return stage_out(c, dst, d_dst, cb, host);
+    return call.done();
 }
 
 // ---- HAVC_stabilizer(stab=True): vs_chroma_stabilizer_ex + vs_reduce_flicker on a clip, chunk by chunk (chroma_stab.hip, tweak.hip) ----
@@ -683,8 +592,7 @@ int havc_chroma_stab_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const h
         return fail(c, HAVC_E_INVALID, "chroma_stab_clip: tht must be 0..256, sat / weight / tht_scen finite");
     if ((p->scene_prev && is_device_ptr(p->scene_prev)) || (p->scene_next && is_device_ptr(p->scene_next)))
         return fail(c, HAVC_E_INVALID, "chroma_stab_clip: the scene-change arrays are host memory");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "chroma_stab_clip");
     const int n = p->n_frames, N = p->n_weights, nh = (N - 1) / 2, halo = p->flicker ? 2 : 0, last = n - 1;
     const bool restore = p->tht > 0;
     const int span = chroma_stab_span(p, halo), core = span - 2 * halo;
@@ -698,11 +606,10 @@ int havc_chroma_stab_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const h
     const size_t o_y = take(A_max * pb), o_u = take((A_max + P_max) * qb), o_v = take((A_max + P_max) * qb), o_au = take(S_max * qb), o_av = take(S_max * qb);
     const size_t o_pairs = take(P_max * fb), o_t = take(p->flicker ? S_max * fb : 0), o_py = take(P_max * sizeof(int)), o_pc = take(P_max * sizeof(int));
     const size_t o_tab = take(S_max * N * sizeof(int)), o_mode = take(P_max), o_stats = take(P_max * 2 * sizeof(unsigned long long));
-    const uint8_t* d_src;
-    uint8_t* d_dst;
-    bool host;
-    if ((rc = stage_in(c, SCR_IN, src, cb, &d_src)) || (rc = stage_out_ptr(c, SCR_OUT, dst, cb, &d_dst, &host)) || (rc = ensure_scratch(c, SCR_CHROMA_STAB, off))) return rc;
-    uint8_t* ws = (uint8_t*)c->scratch[SCR_CHROMA_STAB];
+    const uint8_t* d_src = call.in(SCR_IN, src, cb);
+    uint8_t* d_dst = call.out(SCR_OUT, dst, cb);
+    uint8_t* ws = (uint8_t*)call.scratch(SCR_CHROMA_STAB, off);
+    if (call.rc) return call.rc;
     uint8_t *d_y = ws + o_y, *d_u = ws + o_u, *d_v = ws + o_v, *d_au = ws + o_au, *d_av = ws + o_av, *d_pairs = ws + o_pairs, *d_t = ws + o_t, *d_mode = ws + o_mode;
     int *d_py = (int*)(ws + o_py), *d_pc = (int*)(ws + o_pc), *d_tab = (int*)(ws + o_tab);
     unsigned long long* d_stats = (unsigned long long*)(ws + o_stats);
@@ -744,29 +651,25 @@ int havc_chroma_stab_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const h
         if (!e) e = launch_tweak_back(d_y + (size_t)(s0 - a0) * pb, d_au, d_av, p->flicker ? d_t : d_dst + (size_t)s0 * fb, ba, c->stream);
         c->stats.launches += 2;
         if (!e && p->flicker) { e = launch_reduce_flicker(d_t, s0, d_dst + (size_t)f0 * fb, f0, f1 - f0, last, (int64_t)fb, c->stream); c->stats.launches++; }
-        if (e) return hip_fail(c, (hipError_t)e, "chroma_stab_clip");
+        if (!call.launched(e, 0)) return call.rc;                        // (counted above, launch by launch)
     }
-    return stage_out(c, dst, d_dst, cb, host);
+    return call.done();
 }
 
 int havc_reduce_flicker_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, int width, int height, int n_frames) {
     if (!c || !src || !dst || width <= 0 || height <= 0 || n_frames <= 0 || (int64_t)width * height > ((int64_t)1 << 30))
         return fail(c, HAVC_E_INVALID, "reduce_flicker_clip: bad args (at most 2^30 pixels per frame)");
     if (src == dst) return fail(c, HAVC_E_INVALID, "reduce_flicker_clip: dst must not be src (every output frame reads its neighbours)");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "reduce_flicker_clip");
     const size_t fb = (size_t)width * height * 3, cb = (size_t)n_frames * fb;
-    int rc;
-    const uint8_t* d_src;
-    uint8_t* d_dst;
-    bool host;
-    if ((rc = stage_in(c, SCR_IN, src, cb, &d_src)) || (rc = stage_out_ptr(c, SCR_OUT, dst, cb, &d_dst, &host))) return rc;
+    const uint8_t* d_src = call.in(SCR_IN, src, cb);
+    uint8_t* d_dst = call.out(SCR_OUT, dst, cb);
+    if (call.rc) return call.rc;
     for (int f0 = 0; f0 < n_frames; f0 += 65535) {
         const int e = launch_reduce_flicker(d_src, 0, d_dst + (size_t)f0 * fb, f0, std::min(65535, n_frames - f0), n_frames - 1, (int64_t)fb, c->stream);
-        c->stats.launches++;
-        if (e) return hip_fail(c, (hipError_t)e, "reduce_flicker_clip");
+        if (!call.launched(e)) return call.rc;
     }
-    return stage_out(c, dst, d_dst, cb, host);
+    return call.done();
 }
 
 int havc_adjust_frame_params(const int64_t* chan_sums, int64_t n_pixels, double* out3) {
@@ -785,36 +688,33 @@ int havc_adjust_rgb_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const ha
     if (p->normalize == 2 && !(p->strength > 0.0 && p->strength < 1.0)) return fail(c, HAVC_E_INVALID, "adjust_rgb_clip: strength must be in (0, 1) with normalize 2");
     for (int k = 0; k < 3; ++k)
         if (!(std::isfinite(p->gain[k]) && std::isfinite(p->bias[k]))) return fail(c, HAVC_E_INVALID, "adjust_rgb_clip: gain / bias must be finite");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "adjust_rgb_clip");
     AdjustArgs a{};
     a.n = p->n_frames; a.h = p->height; a.w = p->width; a.mode = p->normalize;
     a.w15 = p->normalize == 2 ? eq_w15(p->strength) : 0;
     for (int k = 0; k < 3; ++k) { a.gain[k] = p->gain[k]; a.bias[k] = p->bias[k]; }
     memcpy(a.gamma_lut, p->gamma_lut, sizeof(a.gamma_lut));
     const size_t cb = (size_t)a.n * a.h * a.w * 3, rb = (size_t)a.n * sizeof(EqFrameRec), tb = (size_t)a.n * 3 * 256;
-    int rc;
-    const uint8_t* d_src;
-    uint8_t* d_dst;
-    bool host;
-    if ((rc = stage_in(c, SCR_IN, src, cb, &d_src)) || (rc = stage_out_ptr(c, SCR_OUT, dst, cb, &d_dst, &host)) || (rc = ensure_scratch(c, SCR_ADJUST_TABLES, rb + tb))) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->scratch[SCR_ADJUST_TABLES], 0, rb, c->stream));
-    const int e = launch_adjust_rgb(d_src, d_dst, c->scratch[SCR_ADJUST_TABLES], (uint8_t*)c->scratch[SCR_ADJUST_TABLES] + rb, a, c->stream);
-    c->stats.launches += a.mode ? 3 : 2;
-    if (e) return hip_fail(c, (hipError_t)e, "adjust_rgb_clip");
-    return stage_out(c, dst, d_dst, cb, host);
+    const uint8_t* d_src = call.in(SCR_IN, src, cb);
+    uint8_t* d_dst = call.out(SCR_OUT, dst, cb);
+    uint8_t* d_sums = (uint8_t*)call.scratch(SCR_ADJUST_TABLES, rb + tb);           // the channel sums, then the tables
+    if (call.rc) return call.rc;
+    call.zero(d_sums, rb);
+    call.launched(launch_adjust_rgb(d_src, d_dst, d_sums, d_sums + rb, a, c->stream), a.mode ? 3 : 2);
+    return call.done();
 }
 
 int havc_luma_lut(havc_ctx* c, const uint8_t* img, const uint8_t* lut256, uint8_t* out, int width, int height) {
     if (!c || !img || !lut256 || !out || width <= 0 || height <= 0) return fail(c, HAVC_E_INVALID, "luma_lut: bad args");
-    return run_filter(c, img, nullptr, out, (size_t)width * height * 3, "luma_lut",
-                      [&](const uint8_t* da, const uint8_t*, uint8_t* dout) {
-                          return launch_luma_lut(da, (const uint8_t*)c->scratch[SCR_SMALL], dout, (int64_t)width * height, c->stream); },
-                      [&]() -> int {
-                          int rc = ensure_scratch(c, SCR_SMALL, 256);
-                          if (rc) return rc;
-                          HIP_TRY(c, hipMemcpyAsync(c->scratch[SCR_SMALL], lut256, 256, hipMemcpyDefault, c->stream));
-                          return HAVC_OK; });
+    Call call(c, "luma_lut");
+    const size_t nb = (size_t)width * height * 3;
+    uint8_t* d_lut = (uint8_t*)call.scratch(SCR_SMALL, 256);
+    call.copy(d_lut, lut256, 256, hipMemcpyDefault);                     // (the table may be host or device memory)
+    const uint8_t* din = call.in(SCR_IN, img, nb);
+    uint8_t* dout = call.out(SCR_OUT, out, nb);
+    if (call.rc) return call.rc;
+    call.launched(launch_luma_lut(din, d_lut, dout, (int64_t)width * height, c->stream));
+    return call.done();
 }
 
 int havc_restore_color_gradient(havc_ctx* c, const uint8_t* img_color, const uint8_t* img_gray, uint8_t* out, int width, int height, double sat,
@@ -837,46 +737,35 @@ int havc_recover_color_clip(havc_ctx* c, const uint8_t* gray, const uint8_t* col
     const size_t cb = (size_t)p->n_frames * p->height * p->width * 3;
     auto overlaps = [&](const uint8_t* q) { return (uintptr_t)out < (uintptr_t)q + cb && (uintptr_t)q < (uintptr_t)out + cb; };
     if (overlaps(gray) || overlaps(color)) return fail(c, HAVC_E_INVALID, "recover_color_clip: out must not alias an input");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "recover_color_clip");
     RecoverArgs a{};
     a.n = p->n_frames; a.h = p->height; a.w = p->width; a.first_frame = p->first_frame;
     a.sat = p->sat; a.weight = p->weight; a.alpha = p->alpha; a.tht = p->tht; a.algo = p->algo;
     a.binary_mask = p->binary_mask != 0; a.return_mask = p->return_mask != 0;
-    int rc;
-    const uint8_t *d_gray, *d_color;
-    uint8_t* d_out;
-    bool host;
-    if ((rc = stage_in(c, SCR_IN, gray, cb, &d_gray)) || (rc = stage_in(c, SCR_IN2, color, cb, &d_color)) ||
-        (rc = stage_out_ptr(c, SCR_OUT, out, cb, &d_out, &host)) || (rc = ensure_scratch(c, SCR_SMALL, (size_t)a.n * sizeof(unsigned long long)))) return rc;
-    const int e = launch_recover_color(d_gray, d_color, d_out, (unsigned long long*)c->scratch[SCR_SMALL], a, c->stream);
-    c->stats.launches += 2;
-    if (e) return hip_fail(c, (hipError_t)e, "recover_color_clip");
-    return stage_out(c, out, d_out, cb, host);
+    const uint8_t *d_gray = call.in(SCR_IN, gray, cb), *d_color = call.in(SCR_IN2, color, cb);
+    uint8_t* d_out = call.out(SCR_OUT, out, cb);
+    unsigned long long* d_sums = (unsigned long long*)call.scratch(SCR_SMALL, (size_t)a.n * sizeof(unsigned long long));
+    if (call.rc) return call.rc;
+    call.launched(launch_recover_color(d_gray, d_color, d_out, d_sums, a, c->stream), 2);
+    return call.done();
 }
 
 int havc_color_temporal_stabilizer(havc_ctx* c, const uint8_t* const* frames, const double* weights, int n, uint8_t* out, int width, int height) {
     if (!c || !frames || !weights || !out || n < 1 || n > 9 || width <= 0 || height <= 0) return fail(c, HAVC_E_INVALID, "color_temporal_stabilizer: bad args (1..9 frames)");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "color_temporal_stabilizer");
     const size_t nb = (size_t)width * height * 3;
-    int rc;
-    if ((rc = ensure_scratch(c, SCR_IN, nb * n))) return rc;
-    uint8_t* dout;
-    bool host;
-    if ((rc = stage_out_ptr(c, SCR_OUT, out, nb, &dout, &host))) return rc;
-    const uint8_t* d_frames[9];
+    Call::Pack host_frames(SCR_IN);
     for (int k = 0; k < n; ++k) {
         if (!frames[k]) return fail(c, HAVC_E_INVALID, "color_temporal_stabilizer: NULL frame");
-        if (is_device_ptr(frames[k])) { d_frames[k] = frames[k]; continue; }
-        uint8_t* d = (uint8_t*)c->scratch[SCR_IN] + nb * k;
-        HIP_TRY(c, hipMemcpyAsync(d, frames[k], nb, hipMemcpyHostToDevice, c->stream));
-        d_frames[k] = d;
+        call.add(host_frames, frames[k], nb);
     }
-    int e = launch_color_temporal_stabilizer(d_frames, weights, n, dout, (int64_t)width * height, c->stream);
-    c->stats.launches++;
-    if (e) return hip_fail(c, (hipError_t)e, "color_temporal_stabilizer");
-    return stage_out(c, out, dout, nb, host);
+    call.reserve(host_frames);
+    uint8_t* dout = call.out(SCR_OUT, out, nb);
+    const uint8_t* d_frames[9];
+    for (int k = 0; k < n; ++k) d_frames[k] = call.in(host_frames, frames[k], nb);
+    if (call.rc) return call.rc;
+    call.launched(launch_color_temporal_stabilizer(d_frames, weights, n, dout, (int64_t)width * height, c->stream));
+    return call.done();
 }
 
 }  // extern "C"

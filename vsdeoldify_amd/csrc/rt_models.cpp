@@ -457,37 +457,30 @@ int havc_colorize_clip_host(havc_ctx* c, havc_net* video, havc_net* second, floa
 int havc_planar_to_rgb8(havc_ctx* c, const uint8_t* const planes[3], int stride, uint8_t* rgb, int width, int height) {
     if (!c || !planes || !rgb || width <= 0 || height <= 0 || stride < width) return fail(c, HAVC_E_INVALID, "planar_to_rgb8: bad args");
     for (int p = 0; p < 3; ++p) if (!planes[p]) return fail(c, HAVC_E_INVALID, "planar_to_rgb8: NULL plane");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "planar_to_rgb8");
     const size_t plane = (size_t)width * height, nb = plane * 3;
-    int rc;
-    uint8_t* dout;
-    bool host;
-    if ((rc = ensure_scratch(c, SCR_PLANES, nb)) || (rc = stage_out_ptr(c, SCR_OUT, rgb, nb, &dout, &host))) return rc;
-    for (int p = 0; p < 3; ++p)
-        HIP_TRY(c, hipMemcpy2DAsync((uint8_t*)c->scratch[SCR_PLANES] + p * plane, (size_t)width, planes[p], (size_t)stride, (size_t)width, (size_t)height, hipMemcpyDefault, c->stream));
-    int e = launch_planar_to_rgb8((const uint8_t*)c->scratch[SCR_PLANES], dout, (int64_t)plane, c->stream);
-    c->stats.launches++;
-    if (e) return hip_fail(c, (hipError_t)e, "planar_to_rgb8");
-    return stage_out(c, rgb, dout, nb, host);
+    uint8_t* d_pl = (uint8_t*)call.scratch(SCR_PLANES, nb);
+    uint8_t* dout = call.out(SCR_OUT, rgb, nb);
+    for (int p = 0; p < 3 && !call.rc; ++p)                              // rows with a stride: packed on their way in
+        call.check(hipMemcpy2DAsync(d_pl + p * plane, (size_t)width, planes[p], (size_t)stride, (size_t)width, (size_t)height, hipMemcpyDefault, c->stream), "hipMemcpy2DAsync");
+    if (call.rc) return call.rc;
+    call.launched(launch_planar_to_rgb8(d_pl, dout, (int64_t)plane, c->stream));
+    return call.done();
 }
 
 int havc_rgb8_to_planar(havc_ctx* c, const uint8_t* rgb, uint8_t* const planes[3], int stride, int width, int height) {
     if (!c || !planes || !rgb || width <= 0 || height <= 0 || stride < width) return fail(c, HAVC_E_INVALID, "rgb8_to_planar: bad args");
     for (int p = 0; p < 3; ++p) if (!planes[p]) return fail(c, HAVC_E_INVALID, "rgb8_to_planar: NULL plane");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "rgb8_to_planar");
     const size_t plane = (size_t)width * height, nb = plane * 3;
-    int rc;
-    const uint8_t* din;
-    if ((rc = stage_in(c, SCR_IN, rgb, nb, &din)) || (rc = ensure_scratch(c, SCR_PLANES, nb))) return rc;
-    int e = launch_rgb8_to_planar(din, (uint8_t*)c->scratch[SCR_PLANES], (int64_t)plane, c->stream);
-    c->stats.launches++;
-    if (e) return hip_fail(c, (hipError_t)e, "rgb8_to_planar");
-    for (int p = 0; p < 3; ++p)
-        HIP_TRY(c, hipMemcpy2DAsync(planes[p], (size_t)stride, (uint8_t*)c->scratch[SCR_PLANES] + p * plane, (size_t)width, (size_t)width, (size_t)height, hipMemcpyDefault, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return HAVC_OK;
+    const uint8_t* din = call.in(SCR_IN, rgb, nb);
+    uint8_t* d_pl = (uint8_t*)call.scratch(SCR_PLANES, nb);
+    if (call.rc) return call.rc;
+    call.launched(launch_rgb8_to_planar(din, d_pl, (int64_t)plane, c->stream));
+    for (int p = 0; p < 3 && !call.rc; ++p)                              // rows with a stride: spread on their way out
+        call.check(hipMemcpy2DAsync(planes[p], (size_t)stride, d_pl + p * plane, (size_t)width, (size_t)width, (size_t)height, hipMemcpyDefault, c->stream), "hipMemcpy2DAsync");
+    call.sync();                                                         // whatever the planes' kind, as ever
+    return call.done();
 }
 
 // One VapourSynth frame through ModelImageRender: the selector body of vs_sc_deoldify (vsslib/vsmodels.py:214-230) --

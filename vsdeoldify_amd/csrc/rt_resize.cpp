@@ -158,16 +158,13 @@ int havc_pil_resize(havc_ctx* c, const uint8_t* src, int sw, int sh, uint8_t* ds
 int havc_pil_resize_n(havc_ctx* c, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, int resample, int n_frames) {
     if (!c || !src || !dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || n_frames < 1 || (resample != 1 && resample != 2 && resample != 3))
         return fail(c, HAVC_E_INVALID, "pil_resize: bad args (resample must be 1 = LANCZOS, 2 = BILINEAR or 3 = BICUBIC)");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
-    int rc;
+    Call call(c, "pil_resize");
     const size_t sb = (size_t)sw * sh * 3 * n_frames, tb = (size_t)sh * dw * 3 * n_frames, db = (size_t)dw * dh * 3 * n_frames;
-    const uint8_t* d_src;
-    uint8_t* d_dst;
-    bool host;
-    if ((rc = stage_in(c, SCR_IN, src, sb, &d_src)) || (rc = ensure_scratch(c, SCR_PIL_ROWS, tb)) || (rc = stage_out_ptr(c, SCR_OUT, dst, db, &d_dst, &host))) return rc;
-    if ((rc = pil_resize_dev(c, d_src, sw, sh, (uint8_t*)c->scratch[SCR_PIL_ROWS], d_dst, dw, dh, n_frames, resample))) return rc;
-    return stage_out(c, dst, d_dst, db, host);
+    const uint8_t* d_src = call.in(SCR_IN, src, sb);
+    uint8_t* d_rows = (uint8_t*)call.scratch(SCR_PIL_ROWS, tb);
+    uint8_t* d_dst = call.out(SCR_OUT, dst, db);
+    if (call.rc || (call.rc = pil_resize_dev(c, d_src, sw, sh, d_rows, d_dst, dw, dh, n_frames, resample))) return call.rc;   // (counts its own launches)
+    return call.done();
 }
 
 int havc_resize_plan(int sw, int dw, int n_rows, int* h_taps, int* h_variant) {
@@ -195,20 +192,15 @@ int havc_spline64_resize_n(havc_ctx* c, const uint8_t* src, int sw, int sh, uint
 int havc_resize_n(havc_ctx* c, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, const uint8_t* luma_from, int n_frames, int filter) {
     if (!c || !src || !dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || n_frames < 1) return fail(c, HAVC_E_INVALID, "resize_n: bad args");
     if (!resize_filter_ok(filter)) return fail(c, HAVC_E_INVALID, "resize: filter must be 0 = Spline64 or 1 = Spline36");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
+    Call call(c, "resize_n");
     const size_t sb = (size_t)sw * sh * 3 * n_frames, db = (size_t)dw * dh * 3 * n_frames;
-    int rc;
-    const uint8_t *d_src, *d_luma = nullptr;
-    uint8_t* d_dst;
-    bool host;
-    if ((rc = stage_in(c, SCR_IN, src, sb, &d_src)) || (rc = stage_out_ptr(c, SCR_OUT, dst, db, &d_dst, &host)) ||
-        (luma_from && (rc = stage_in(c, SCR_IN3, luma_from, db, &d_luma)))) return rc;
-    if (sw == dw && sh == dh && !luma_from) {
-        HIP_TRY(c, hipMemcpyAsync(d_dst, d_src, sb, hipMemcpyDeviceToDevice, c->stream));
-    } else if ((rc = resize_rgb8(c, d_src, sw, sh, d_dst, dw, dh, n_frames, d_luma, filter)))
-        return rc;
-    return stage_out(c, dst, d_dst, db, host);
+    const uint8_t* d_src = call.in(SCR_IN, src, sb);
+    uint8_t* d_dst = call.out(SCR_OUT, dst, db);
+    const uint8_t* d_luma = call.in(SCR_IN3, luma_from, db);             // optional: NULL stays NULL
+    if (call.rc) return call.rc;
+    if (sw == dw && sh == dh && !luma_from) call.copy(d_dst, d_src, sb, hipMemcpyDeviceToDevice);
+    else if ((call.rc = resize_rgb8(c, d_src, sw, sh, d_dst, dw, dh, n_frames, d_luma, filter))) return call.rc;   // (counts its own launches, sizes SCR_RESIZE_ROWS itself)
+    return call.done();
 }
 
 }  // extern "C"

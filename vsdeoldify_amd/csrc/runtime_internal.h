@@ -63,9 +63,10 @@ struct ResizeTable {
 
 // ---- the scratch pool: havc_ctx::scratch[slot], grow-only (ensure_scratch), reused every call.  This enum is the one record of who owns which slot. ----
 // Enumerators that share a value sit on adjacent lines.  Sharing is safe because every user of a shared slot holds c->mu for its whole call and leaves
-// nothing behind in it.  The exception are SCR_BANK_*: they carry state ACROSS calls and therefore share with nobody.
+// nothing behind in it; WITHIN a call the scope (Call, below) refuses a second claim of a slot, so two names of one value cannot meet in one entry point
+// unnoticed.  The exception are SCR_BANK_*: they carry state ACROSS calls and therefore share with nobody.
 enum ScratchSlot {
-    // 0-5: host operands on their way to the device and results on their way back (stage_in / stage_out_ptr; device operands are used in place)
+    // 0-5: host operands on their way to the device and results on their way back (Call::in / Call::out; device operands are used in place)
     SCR_IN = 0,                        // first operand: the image / clip of a filter, the frames entering a model; fp32 ColorMNet ops: mk / q / L plane
     SCR_IN2 = 1,                       // second operand: image b of a two-input filter; ColorMNet: qk / k / ab
     SCR_VIDEO = SCR_IN2,               //   DeOldify drivers: raw colour of the video model
@@ -238,57 +239,152 @@ inline bool is_device_ptr(const void* p) {
     return at.type == hipMemoryTypeDevice;
 }
 
-inline int stage_in(havc_ctx* c, int slot, const void* p, size_t nbytes, const uint8_t** d) {
-    if (is_device_ptr(p)) { *d = (const uint8_t*)p; return HAVC_OK; }
-    int rc = ensure_scratch(c, slot, nbytes);
-    if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->scratch[slot], p, nbytes, hipMemcpyHostToDevice, c->stream));
-    *d = (const uint8_t*)c->scratch[slot];
-    return HAVC_OK;
-}
+// One entry point's use of that protocol.  The scope holds c->mu and has made c->dev current; it stages operands, counts launches, and hands host results
+// back with ONE synchronisation at the end.  Its rc, once non-zero, turns every later member into a no-op that returns NULL: an entry point stages all
+// its operands, looks at rc once, launches, and returns done().  Stream order within a call: uploads, memsets, launches, downloads.
+struct Call {
+    havc_ctx* const c;
+    const char* const what;            // the entry point: every message of the scope starts with it
+    int rc = HAVC_OK;
 
-inline int stage_in_f(havc_ctx* c, int slot, const void* p, size_t nbytes, const float** d) {
-    const uint8_t* q = nullptr;
-    int rc = stage_in(c, slot, p, nbytes, &q);
-    *d = reinterpret_cast<const float*>(q);
-    return rc;
-}
+    // Several operands in ONE slot: add() each, reserve(), then in() / out() each in the order of the add()s.  The slot is sized before the first copy into
+    // it, because ensure_scratch frees and re-allocates a slot that grows, and growing it after a copy would lose that copy: placing an operand before
+    // reserve(), or beyond what the add()s reserved, is refused and never regrows the slot.
+    struct Pack {
+        int slot;
+        size_t need = 0, at = 0;       // bytes the host operands take (each rounded up to 256) / bytes placed so far
+        unsigned host = 0;             // bit i: operand i is host memory (asked once, in add())
+        int n = 0, placed = 0;
+        uint8_t* base = nullptr;       // set by reserve()
+        explicit Pack(int s) : slot(s) {}
+    };
 
-inline int stage_out_ptr(havc_ctx* c, int slot, void* p, size_t nbytes, uint8_t** d, bool* host) {
-    *host = !is_device_ptr(p);
-    if (!*host) { *d = (uint8_t*)p; return HAVC_OK; }
-    int rc = ensure_scratch(c, slot, nbytes);
-    if (rc) return rc;
-    *d = (uint8_t*)c->scratch[slot];
-    return HAVC_OK;
-}
+    Call(havc_ctx* ctx, const char* w) : c(ctx), what(w), lk(ctx->mu) { check(hipSetDevice(c->dev), "hipSetDevice"); }
 
-inline int stage_out(havc_ctx* c, void* p, const uint8_t* d, size_t nbytes, bool host) {
-    if (!host) return HAVC_OK;
-    HIP_TRY(c, hipMemcpyAsync(p, d, nbytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return HAVC_OK;
-}
+    // a HIP status: the first failure becomes rc; true while the call is good
+    bool check(hipError_t e, const char* op) {
+        if (!rc && e != hipSuccess) rc = hip_fail(c, e, (std::string(what) + ": " + op).c_str());
+        return !rc;
+    }
+
+    // A slot's memory, at least nbytes of it.  A call claims a slot ONCE, whatever the kinds of its operands: slots are shared between entry points on the
+    // strength of "one user at a time" (ScratchSlot), and two operands of one call in one slot would overwrite each other.  They belong in a Pack.
+    void* scratch(int slot, size_t nbytes) {
+        if (!claim(slot) || (rc = ensure_scratch(c, slot, nbytes))) return nullptr;
+        return c->scratch[slot];
+    }
+
+    // an input operand on the device: p itself, or its upload into `slot`.  An absent (NULL) optional operand stays NULL.
+    template <typename T>
+    const T* in(int slot, const T* p, size_t nbytes) {
+        if (!p || !claim(slot) || is_device_ptr(p)) return rc ? nullptr : p;
+        return (const T*)upload(scratch_of(slot, nbytes), p, nbytes);
+    }
+    template <typename T>
+    const T* in(Pack& k, const T* p, size_t nbytes) {
+        bool host;
+        void* d = place(k, p, nbytes, &host);
+        return (const T*)(host ? upload(d, p, nbytes) : d);
+    }
+
+    // where the kernels write a result: p itself, or room in `slot` that done() copies back to p
+    template <typename T>
+    T* out(int slot, T* p, size_t nbytes) {
+        if (!p || !claim(slot) || is_device_ptr(p)) return rc ? nullptr : p;
+        return (T*)download(p, scratch_of(slot, nbytes), nbytes);
+    }
+    template <typename T>
+    T* out(Pack& k, T* p, size_t nbytes) {
+        bool host;
+        void* d = place(k, p, nbytes, &host);
+        return (T*)(host ? download(p, d, nbytes) : d);
+    }
+
+    void add(Pack& k, const void* p, size_t nbytes) {
+        if (!is_device_ptr(p)) { k.host |= 1u << k.n; k.need += pack_room(nbytes); }
+        ++k.n;
+    }
+    void reserve(Pack& k) {
+        if (claim(k.slot) && k.need && !(rc = ensure_scratch(c, k.slot, k.need))) k.base = (uint8_t*)c->scratch[k.slot];
+    }
+
+    // a host result that is no operand (records, sums): done() copies nbytes from d to host.  Returns d.
+    void* download(void* host, void* d, size_t nbytes) {
+        if (rc) return nullptr;
+        if (n_back == MAX_BACK) { rc = fail(c, HAVC_E_INVALID, std::string(what) + ": too many host results in one call"); return nullptr; }
+        back[n_back++] = {host, d, nbytes};
+        return d;
+    }
+
+    void zero(void* d, size_t nbytes) { if (!rc) check(hipMemsetAsync(d, 0, nbytes, c->stream), "hipMemsetAsync"); }
+    // a copy enqueued NOW: a table on its way in, a result that leaves a buffer the call is about to reuse.  One into host memory makes done() wait for it.
+    void copy(void* dst, const void* src, size_t nbytes, hipMemcpyKind kind) {
+        if (!rc && check(hipMemcpyAsync(dst, src, nbytes, kind, c->stream), "hipMemcpyAsync") && kind == hipMemcpyDeviceToHost) pending = true;
+    }
+    // for the call that needs a result in the middle (a sum the next launch depends on)
+    void sync() {
+        if (!rc) check(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+        pending = false;
+    }
+
+    bool launched(int e, int n = 1) {
+        if (rc) return false;
+        c->stats.launches += n;
+        if (e) rc = hip_fail(c, (hipError_t)e, what);
+        return !rc;
+    }
+
+    // every host result goes back, then ONE synchronisation -- if and only if there was one: a call with device results only has enqueued and returns
+    int done() {
+        for (int i = 0; i < n_back; ++i) copy(back[i].host, back[i].dev, back[i].nbytes, hipMemcpyDeviceToHost);
+        if (pending) sync();
+        return rc;
+    }
+
+  private:
+    enum { MAX_BACK = 8 };
+    std::lock_guard<std::mutex> lk;
+    unsigned claimed = 0;              // bit per ScratchSlot this call has claimed
+    bool pending = false;              // a device-to-host copy is on the stream and nobody has waited for it yet
+    struct { void* host; const void* dev; size_t nbytes; } back[MAX_BACK];
+    int n_back = 0;
+
+    static size_t pack_room(size_t nbytes) { return (nbytes + 255) & ~(size_t)255; }
+    bool claim(int slot) {
+        if (rc) return false;
+        if (claimed & (1u << slot)) { rc = fail(c, HAVC_E_INVALID, std::string(what) + ": scratch slot " + std::to_string(slot) + " claimed twice in one call"); return false; }
+        claimed |= 1u << slot;
+        return true;
+    }
+    void* scratch_of(int slot, size_t nbytes) { return (rc = ensure_scratch(c, slot, nbytes)) ? nullptr : c->scratch[slot]; }   // of a slot already claimed
+    void* upload(void* d, const void* p, size_t nbytes) {
+        if (d) copy(d, p, nbytes, hipMemcpyHostToDevice);
+        return rc ? nullptr : d;
+    }
+    void* place(Pack& k, const void* p, size_t nbytes, bool* host) {
+        *host = false;
+        if (rc) return nullptr;
+        const int i = k.placed++;
+        const bool added = i < k.n, on_host = added && ((k.host >> i) & 1);
+        if (added && !on_host) return const_cast<void*>(p);
+        if (!added || !k.base || k.at + pack_room(nbytes) > k.need) {
+            rc = fail(c, HAVC_E_INVALID, std::string(what) + ": the pack in scratch slot " + std::to_string(k.slot) + " places an operand before reserve(), or beyond what was reserved");
+            return nullptr;
+        }
+        *host = true;
+        void* d = k.base + k.at;
+        k.at += pack_room(nbytes);
+        return d;
+    }
+};
 
 // two-input (b may be NULL) / one-output per-pixel filter: stage, launch, hand back
-template <typename Launch, typename Pre>
-inline int run_filter(havc_ctx* c, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t nbytes, const char* what, Launch launch, Pre pre) {
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(c, hipSetDevice(c->dev));
-    const uint8_t *da = nullptr, *db = nullptr;
-    uint8_t* dout = nullptr;
-    bool host = false;
-    int rc;
-    if ((rc = pre())) return rc;
-    if ((rc = stage_in(c, SCR_IN, a, nbytes, &da))) return rc;
-    if (b && (rc = stage_in(c, SCR_IN2, b, nbytes, &db))) return rc;
-    if ((rc = stage_out_ptr(c, SCR_OUT, out, nbytes, &dout, &host))) return rc;
-    const int e = launch(da, db, dout);
-    c->stats.launches++;
-    if (e) return hip_fail(c, (hipError_t)e, what);
-    return stage_out(c, out, dout, nbytes, host);
-}
 template <typename Launch>
 inline int run_filter(havc_ctx* c, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t nbytes, const char* what, Launch launch) {
-    return run_filter(c, a, b, out, nbytes, what, launch, []() { return HAVC_OK; });
+    Call call(c, what);
+    const uint8_t *da = call.in(SCR_IN, a, nbytes), *db = call.in(SCR_IN2, b, nbytes);
+    uint8_t* dout = call.out(SCR_OUT, out, nbytes);
+    if (call.rc) return call.rc;
+    call.launched(launch(da, db, dout));
+    return call.done();
 }
