@@ -709,6 +709,45 @@ typedef struct havc_adjust_params {
 int havc_adjust_rgb_clip(havc_ctx* ctx, const uint8_t* src, uint8_t* dst, const havc_adjust_params* params);
 /* the gains of normalize != 0 from a frame's three channel sums, on the host (no context, no GPU): out3 in float64 */
 int havc_adjust_frame_params(const int64_t* chan_sums, int64_t n_pixels, double* out3);
+/* HAVC_TimeCube's 3D LUT (vsdeoldify/__init__.py:2995-3026 -> vs_timecube_load, vsslib/vsplugins.py:283-323 -> the timecube.Cube plugin) on a clip
+ * [n_frames][height][width][3].  The plugin cannot be executed where the fixtures are made: trilinear interpolation as an UNPINNED stand-in whose definition is
+ * tests/timecube_util.py, and the kernel equals it byte for byte.  table: [size^3][3] floats as a .cube file lists them (red index fastest, blue slowest), finite.
+ * The samples are 8 bit, so the caller hands in what each of the 256 values of channel c means: idx[c][v], the lower lattice index of its cell (0 .. size - 2;
+ * anything else is clamped to that range), and frac[c][v], its position inside the cell (vsdeoldify_amd/timecube.py axis_tables derives both from the file's
+ * domain).  Per pixel, float32, one rounding per operation, never fused: the eight points around (idx_r, idx_g, idx_b); per output channel seven
+ * lerp(a, b, f) = a + (b - a) * f -- four along red with frac_r, two along green with frac_g, one along blue with frac_b; out = rint(min(max(v, 0), 1) * 255),
+ * half to even.  Two launches: the table is copied into 16-byte points (one aligned load per corner), then one pass over all frames. */
+typedef struct havc_lut3d_params {
+    int width, height, n_frames;  /* at most 2^30 pixels per frame */
+    int size;                     /* lattice points per axis: 2..256 */
+} havc_lut3d_params;
+/* src, dst, table: host or device pointers, each on its own; idx, frac: [3][256], host or device.  Device operands: the call only enqueues.  A NULL pointer,
+ * dst == src, a non-positive or oversized frame, size outside 2..256: HAVC_E_INVALID, nothing runs. */
+int havc_lut3d_clip(havc_ctx* ctx, const uint8_t* src, uint8_t* dst, const float* table, const int32_t* idx, const float* frac, const havc_lut3d_params* params);
+/* HAVC_clip_overlay (vsdeoldify/__init__.py:3029-3148) on RGB24 clips: overlay [overlay_frames][ov_h][ov_w][3] is put on base [n_frames][base_h][base_w][3]
+ * with its top left corner at (x, y), either sign; dst has the base's shape.  std.Crop, std.AddBorders, std.Expr and std.MaskedMerge are native VapourSynth: an
+ * UNPINNED stand-in whose definition is tests/overlay_util.py, and the kernel equals it byte for byte.  Nothing is cropped or padded: a pixel outside the placed
+ * overlay, and a plane that is not in plane_mask, keeps the base's sample.  Inside, per processed plane k, with b the base's sample and x the overlay's:
+ *   m = the mask's sample -- 255 without a mask; [ov_h][ov_w] (mask_planes 1) serves every plane, as does plane 0 of [ov_h][ov_w][3] (mask_planes 3) with
+ *       mask_first_plane != 0, else plane k; with opacity < 1, m = expr8(float32(m) * opacity);
+ *   o = x (mode 0, normal), else expr8(f(x, b)) in float32, one rounding per operation, IEEE division:  1 addition x + b;  2 average (x + b) / 2;
+ *       3 difference |x - b|;  4 divide b <= 0 ? 255 : (255 x) / b;  5 exclusion (x + b) - ((2 x) b) / 255;  6 multiply (x b) / 255;
+ *       7 overlay x < 128 ? 2 ((x b) / 255) : 255 - 2 (((255 - x) (255 - b)) / 255);  8 subtract x - b;
+ *   expr8(v) = (int)(min(max(v, 0), 255) + 0.5);   out = (b (255 - m) + o m + 127) / 255, rounded down (the std.MaskedMerge stand-in of havc_tile_reconstruct). */
+typedef struct havc_overlay_params {
+    int base_w, base_h, ov_w, ov_h;   /* at most 2^30 pixels per frame each */
+    int n_frames;
+    int x, y;                         /* within +-2^30 */
+    int mode;                         /* 0..8, above */
+    int plane_mask;                   /* bit k: plane k is processed */
+    int mask_planes;                  /* 0 (mask NULL), 1 or 3 */
+    int mask_first_plane;
+    int overlay_frames;               /* 1 (the one frame is repeated) or n_frames; the mask has as many frames as the overlay */
+    float opacity;                    /* in [0, 1] */
+    int reserved;
+} havc_overlay_params;
+/* base, overlay, mask, dst: host or device pointers, each on its own; dst is none of the inputs.  Device operands: the call only enqueues.  One launch. */
+int havc_overlay_clip(havc_ctx* ctx, const uint8_t* base, const uint8_t* overlay, const uint8_t* mask, uint8_t* dst, const havc_overlay_params* params);
 /* the per-pixel half of luma_adjusted_levels (vsslib/imfilters.py:335-372): cv2 RGB->YUV, Y' = lut[Y], YUV->RGB.  The caller
  * derives the 256-entry table from havc_image_luma exactly like the reference (vsdeoldify_amd/imfilters.py). */
 int havc_luma_lut(havc_ctx* ctx, const uint8_t* img, const uint8_t* lut256, uint8_t* out, int width, int height);

@@ -22,7 +22,8 @@ def __getattr__(name):
     if name in ("HAVC_colorizer", "HAVC_merge", "HAVC_ddeoldify", "ddeoldify", "HAVC_stabilizer", "HAVC_stabilizer_scenes", "HAVCFrameColorizer", "HAVC_clip_slice",
                 "HAVC_clip_reconstruct", "ClipTiles", "tiled_preset_params", "HAVC_SceneDetect", "HAVC_deepex", "HAVC_auto_levels", "HAVC_bw_tune",
                 "HAVC_DeepRemaster", "HAVC_extract_reference_frames", "HAVC_export_reference_frames", "HAVC_export_list_frames",
-                "HAVC_recover_clip_color", "HAVC_restore_video", "HAVC_retinex", "HAVC_SceneDetectEdges", "HAVC_tweak", "HAVC_adjust_rgb", "HAVC_rgb_denoise"):
+                "HAVC_recover_clip_color", "HAVC_restore_video", "HAVC_retinex", "HAVC_SceneDetectEdges", "HAVC_tweak", "HAVC_adjust_rgb", "HAVC_rgb_denoise",
+                "HAVC_TimeCube", "HAVC_clip_overlay"):
         from . import havc
         return getattr(havc, name)
     if name in ("RemasterRender", "RemasterClipRender"):

@@ -122,6 +122,18 @@ class AdjustParams(C.Structure):
                 ("bias", C.c_float * 3), ("gamma_lut", (C.c_uint8 * 256) * 3)]
 
 
+class Lut3dParams(C.Structure):
+    """`havc_lut3d_params` (include/havc_mi355.h): clip size and lattice points per axis of havc_lut3d_clip"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int), ("size", C.c_int)]
+
+
+class OverlayParams(C.Structure):
+    """`havc_overlay_params` (include/havc_mi355.h): the two clip sizes, the placement, blend mode, planes, mask layout and opacity of havc_overlay_clip"""
+    _fields_ = [("base_w", C.c_int), ("base_h", C.c_int), ("ov_w", C.c_int), ("ov_h", C.c_int), ("n_frames", C.c_int), ("x", C.c_int), ("y", C.c_int),
+                ("mode", C.c_int), ("plane_mask", C.c_int), ("mask_planes", C.c_int), ("mask_first_plane", C.c_int), ("overlay_frames", C.c_int),
+                ("opacity", C.c_float), ("reserved", C.c_int)]
+
+
 class RecoverParams(C.Structure):
     """`havc_recover_params` (include/havc_mi355.h): clip size, first frame number and the arguments of ChromaRetentionMerge's selectors (havc_recover_color_clip)"""
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int), ("first_frame", C.c_int), ("sat", C.c_double), ("tht", C.c_int),
@@ -221,6 +233,8 @@ SYMBOLS = [
     ("havc_reduce_flicker_clip", _I, [_P, _P, _P, _I, _I, _I]),
     ("havc_adjust_rgb_clip", _I, [_P, _P, _P, _P]),
     ("havc_adjust_frame_params", _I, [_P, C.c_int64, _P]),
+    ("havc_lut3d_clip", _I, [_P, _P, _P, _P, _P, _P, _P]),
+    ("havc_overlay_clip", _I, [_P, _P, _P, _P, _P, _P]),
     ("havc_luma_lut", _I, [_P, _P, _P, _P, _I, _I]),
     ("havc_restore_color_gradient", _I, [_P, _P, _P, _P, _I, _I, _D, _I, _D, _D, _I, _I]),
     ("havc_recover_color_clip", _I, [_P, _P, _P, _P, _P]),

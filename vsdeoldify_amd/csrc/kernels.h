@@ -307,6 +307,20 @@ struct AdjustArgs {
 };
 // rec: n zero-filled EqFrameRec (used with mode != 0); tables: n * 768 bytes; both device memory
 int launch_adjust_rgb(const uint8_t* src, uint8_t* dst, void* rec, uint8_t* tables, AdjustArgs a, hipStream_t s);
+// lut3d.hip: HAVC_TimeCube's 3D LUT on a clip, trilinear (the stand-in of tests/timecube_util.py).  table: [size^3][3] floats, red fastest; points: room for
+// size^3 * 16 bytes (the padded copy the first launch writes); idx / frac: the axis tables [3][256]; all device memory.  Two launches.
+struct Lut3dArgs { int64_t npix; int size; };     // pixels of the whole clip; lattice points per axis (2..256)
+int launch_lut3d(const uint8_t* src, uint8_t* dst, const float* table, void* points, const int* idx, const float* frac, Lut3dArgs a, hipStream_t s);
+// overlay.hip: HAVC_clip_overlay on RGB24 clips (the stand-in of tests/overlay_util.py), one launch
+struct OverlayArgs {
+    int n, bw, bh, ow, oh;        // frames; base and overlay size
+    int x, y;                     // where the overlay's top left corner lies on the base (either sign)
+    int mode, plane_mask;         // OverlayMode (overlay_ops.h); bit k: plane k is processed
+    int mask_planes, first_plane; // 0: no mask, 1: [oh][ow], 3: [oh][ow][3]; first_plane != 0: plane 0 of a 3-plane mask serves every plane
+    int overlay_frames;           // 1 (repeated) or n; the mask has as many
+    float opacity;
+};
+int launch_overlay(const uint8_t* base, const uint8_t* ov, const uint8_t* mask, uint8_t* dst, OverlayArgs a, hipStream_t s);
 // separable polyphase resample of interleaved u8 RGB (tap tables from the host; Spline64 = harness stand-in
 // for zimg resize.Spline64).  orig != null fuses chroma_post_process (luma of orig, chroma of the resampled).
 int launch_resize_passes(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, int n_frames, float* tmp,
@@ -360,6 +374,8 @@ void preload_equalize();
 void preload_retinex();
 void preload_tweak_clip();
 void preload_chroma_stab();
+void preload_lut3d();
+void preload_overlay();
 void preload_ddcolor();
 void preload_colormnet();
 void preload_colormnet_net();

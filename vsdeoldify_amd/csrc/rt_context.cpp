@@ -88,7 +88,7 @@ static void preload_device_locked(int dev) {
     static uint64_t done = 0;                              // guarded by g_setup_mu
     if (done & (1ull << (dev & 63))) return;
     preload_conv_pipe(); preload_conv_igemm(); preload_elementwise(); preload_zhang(); preload_attention(); preload_colorfilters();
-    preload_tweaks(); preload_stabilizer(); preload_tiles(); preload_scdetect(); preload_scfilter(); preload_scedge(); preload_equalize(); preload_retinex(); preload_tweak_clip(); preload_chroma_stab(); preload_recover(); preload_ddcolor(); preload_colormnet(); preload_colormnet_net(); preload_precise(); preload_precise2(); preload_remaster();
+    preload_tweaks(); preload_stabilizer(); preload_tiles(); preload_scdetect(); preload_scfilter(); preload_scedge(); preload_equalize(); preload_retinex(); preload_tweak_clip(); preload_chroma_stab(); preload_lut3d(); preload_overlay(); preload_recover(); preload_ddcolor(); preload_colormnet(); preload_colormnet_net(); preload_precise(); preload_precise2(); preload_remaster();
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(scratch_warm_kernel));
     (void)hipGetLastError();

@@ -7,6 +7,8 @@
 #include "retinex_ops.h"
 #include "tweak_ops.h"
 #include "chroma_stab_ops.h"
+#include "lut3d_ops.h"
+#include "overlay_ops.h"
 
 extern "C" {
 
@@ -765,6 +767,65 @@ int havc_color_temporal_stabilizer(havc_ctx* c, const uint8_t* const* frames, co
     for (int k = 0; k < n; ++k) d_frames[k] = call.in(host_frames, frames[k], nb);
     if (call.rc) return call.rc;
     call.launched(launch_color_temporal_stabilizer(d_frames, weights, n, dout, (int64_t)width * height, c->stream));
+    return call.done();
+}
+
+// ---- HAVC_TimeCube's 3D LUT on a clip (lut3d.hip) ----
+static_assert(sizeof(havc_lut3d_params) == 16, "havc_lut3d_params layout");
+
+int havc_lut3d_clip(havc_ctx* c, const uint8_t* src, uint8_t* dst, const float* table, const int32_t* idx, const float* frac, const havc_lut3d_params* p) {
+    if (!c || !src || !dst || !table || !idx || !frac || !p) return fail(c, HAVC_E_INVALID, "lut3d_clip: bad args");
+    if (src == dst) return fail(c, HAVC_E_INVALID, "lut3d_clip: dst must not be src");
+    if (p->n_frames <= 0 || p->width <= 0 || p->height <= 0 || (int64_t)p->width * p->height > ((int64_t)1 << 30))
+        return fail(c, HAVC_E_INVALID, "lut3d_clip: bad clip size (at most 2^30 pixels per frame)");
+    if (p->size < LUT3D_MIN_SIZE || p->size > LUT3D_MAX_SIZE) return fail(c, HAVC_E_INVALID, "lut3d_clip: size must be 2..256");
+    Call call(c, "lut3d_clip");
+    Lut3dArgs a{};
+    a.npix = (int64_t)p->n_frames * p->height * p->width; a.size = p->size;
+    const size_t cb = (size_t)a.npix * 3, points = (size_t)a.size * a.size * a.size, pb = points * sizeof(Lut3dPoint), tb = points * 3 * sizeof(float);
+    const size_t ab = 3 * 256 * sizeof(int32_t);
+    const bool host_table = !is_device_ptr(table);
+    const uint8_t* d_src = call.in(SCR_IN, src, cb);
+    uint8_t* d_dst = call.out(SCR_OUT, dst, cb);
+    uint8_t* d_points = (uint8_t*)call.scratch(SCR_LUT3D, pb + (host_table ? tb : 0));      // the points, then a host table on its way in
+    uint8_t* d_axes = (uint8_t*)call.scratch(SCR_SMALL, 2 * ab);                            // idx, then frac
+    if (call.rc) return call.rc;
+    if (host_table) { call.copy(d_points + pb, table, tb, hipMemcpyHostToDevice); table = (const float*)(d_points + pb); }
+    call.copy(d_axes, idx, ab, hipMemcpyDefault);                        // (the axis tables may be host or device memory)
+    call.copy(d_axes + ab, frac, ab, hipMemcpyDefault);
+    if (call.rc) return call.rc;
+    call.launched(launch_lut3d(d_src, d_dst, table, d_points, (const int*)d_axes, (const float*)(d_axes + ab), a, c->stream), 2);
+    return call.done();
+}
+
+// ---- HAVC_clip_overlay (overlay.hip) ----
+static_assert(sizeof(havc_overlay_params) == 56, "havc_overlay_params layout");
+
+int havc_overlay_clip(havc_ctx* c, const uint8_t* base, const uint8_t* overlay, const uint8_t* mask, uint8_t* dst, const havc_overlay_params* p) {
+    if (!c || !base || !overlay || !dst || !p) return fail(c, HAVC_E_INVALID, "overlay_clip: bad args");
+    if (dst == base || dst == overlay || dst == mask) return fail(c, HAVC_E_INVALID, "overlay_clip: dst must not be an input");
+    const int64_t lim = (int64_t)1 << 30;
+    if (p->n_frames <= 0 || p->base_w <= 0 || p->base_h <= 0 || p->ov_w <= 0 || p->ov_h <= 0 || (int64_t)p->base_w * p->base_h > lim || (int64_t)p->ov_w * p->ov_h > lim)
+        return fail(c, HAVC_E_INVALID, "overlay_clip: bad clip size (at most 2^30 pixels per frame)");
+    if (p->x <= -lim || p->x >= lim || p->y <= -lim || p->y >= lim) return fail(c, HAVC_E_INVALID, "overlay_clip: x and y must lie within +-2^30");
+    if (p->mode < 0 || p->mode >= OV_MODES) return fail(c, HAVC_E_INVALID, "overlay_clip: mode must be 0..8");
+    if (p->plane_mask < 0 || p->plane_mask > 7) return fail(c, HAVC_E_INVALID, "overlay_clip: plane_mask must be 0..7");
+    if ((p->mask_planes != 0 && p->mask_planes != 1 && p->mask_planes != 3) || (p->mask_planes != 0) != (mask != nullptr))
+        return fail(c, HAVC_E_INVALID, "overlay_clip: mask_planes must be 0 (and no mask), 1 or 3 (and a mask)");
+    if (p->overlay_frames != 1 && p->overlay_frames != p->n_frames) return fail(c, HAVC_E_INVALID, "overlay_clip: overlay_frames must be 1 or n_frames");
+    if (!(p->opacity >= 0.f && p->opacity <= 1.f)) return fail(c, HAVC_E_INVALID, "overlay_clip: opacity must be in [0, 1]");
+    Call call(c, "overlay_clip");
+    OverlayArgs a{};
+    a.n = p->n_frames; a.bw = p->base_w; a.bh = p->base_h; a.ow = p->ov_w; a.oh = p->ov_h; a.x = p->x; a.y = p->y;
+    a.mode = p->mode; a.plane_mask = p->plane_mask; a.mask_planes = p->mask_planes; a.first_plane = p->mask_first_plane != 0;
+    a.overlay_frames = p->overlay_frames; a.opacity = p->opacity;
+    const size_t bb = (size_t)a.n * a.bh * a.bw * 3, op = (size_t)a.overlay_frames * a.oh * a.ow;
+    const uint8_t* d_base = call.in(SCR_IN, base, bb);
+    const uint8_t* d_ov = call.in(SCR_IN2, overlay, op * 3);
+    const uint8_t* d_mask = call.in(SCR_IN3, mask, op * (size_t)a.mask_planes);               // NULL without a mask
+    uint8_t* d_dst = call.out(SCR_OUT, dst, bb);
+    if (call.rc) return call.rc;
+    call.launched(launch_overlay(d_base, d_ov, d_mask, d_dst, a, c->stream));
     return call.done();
 }
 

@@ -89,6 +89,7 @@ enum ScratchSlot {
     SCR_TWEAK_YUV = SCR_RESIZE_ROWS,        //   havc_tweak_clip: the Y, then U, then V planes of a CHUNK of frames between the two conversions; the two halves on
                                             //   their own (havc_rgb_to_yuv420 / havc_yuv420_to_rgb): host planes on their way in or out
     SCR_CHROMA_STAB = SCR_RESIZE_ROWS,      //   havc_chroma_stab_clip: the workspace of a CHUNK of frames -- planes, the shifted clips, tables, sums (bounded by the chunk)
+    SCR_LUT3D = SCR_RESIZE_ROWS,            //   havc_lut3d_clip: the table as 16-byte points, and in front of them a host table on its way in
     // 8-11: the pipelined host clip (havc_colorize_clip_host), double-buffered by batch parity; the ONE-SHOT ColorMNet reads reuse them
     SCR_CLIP_SRC = 8,                  // 8, 9: source batches, SCR_CLIP_SRC + (batch & 1)
     SCR_SIM = SCR_CLIP_SRC,            //   one-shot read: similarity map [B][N][HW]; havc_local_attention: the attention map

@@ -16,6 +16,8 @@
     HAVC_tweak       vsdeoldify/__init__.py:1377-1408     (hue, saturation, brightness, contrast, gamma through a YUV420P8 round trip; tweak.py)
     HAVC_adjust_rgb  vsdeoldify/__init__.py:1342-1374     (grey-world normalisation, per-channel gain, bias and gamma as per-frame tables; tweak.py)
     HAVC_rgb_denoise vsdeoldify/__init__.py:924-944       (rgb_balance + CLAHE on luma between the TV-range conversions: the equalize.py path)
+    HAVC_TimeCube    vsdeoldify/__init__.py:2995-3026     (a 3D LUT from a .cube file, vs_tweak with the effect's factors, merge by strength; timecube.py)
+    HAVC_clip_overlay vsdeoldify/__init__.py:3029-3148    (an overlay placed on a base: nine blend modes, mask, opacity, planes; overlay.py)
 
 Same names, argument lists, defaults, parameter normalisation, frame-size rule, model routing, combine dispatch
 (vsslib/mcomb.py:125-192) and error texts; a "clip" is a uint8 array [n, h, w, 3] (or one frame [h, w, 3], or a
@@ -67,6 +69,12 @@ contract; none of it can be executed where the fixtures are made
     float32 sequences of tests/tweak_util.py, which csrc/tweak.hip equals byte for byte; none of it can be executed where the fixtures are made.  What
     vs_tweak, adjust_rgb, vs_rgb_normalize and rgb_denoise hand to those filters is the reference's Python, restated and pinned by tests/golden/tweak.npz.
     The `vs_tweak` refusals INSIDE the other entry points (HAVC_colorizer's sat / hue, HAVC_DeepRemaster / HAVC_restore_video render_vivid, ddtweak) stay exactly as they are: existing tests pin them, and routing them to the new code is a separate decision.
+  * HAVC_TimeCube (vsdeoldify_amd/timecube.py has the details): the `timecube.Cube` plugin -> trilinear interpolation in the .cube file's table, float32, restated
+    in tests/timecube_util.py, which csrc/lut3d.hip equals byte for byte -- the plugin is not in the reference tree.  The file names, the factors handed to
+    vs_tweak and the merges are the reference's Python, restated and pinned by tests/golden/timecube.npz.  A LUT file that is not there is an ERROR here (the
+    reference logs and goes on with the un-graded clip).  rgb_equalizer(method=4) / HAVC_bw_tune(bw_method=4) are not routed here yet and stay refused.
+  * HAVC_clip_overlay (vsdeoldify_amd/overlay.py has the details): `std.Crop`, `std.AddBorders`, `std.Expr` and `std.MaskedMerge` -> the sequences of
+    tests/overlay_util.py, which csrc/overlay.hip equals byte for byte; RGB24 only.
 HAVC_clip_slice pads where the reference's std.CropAbs would leave the padded clip by one pixel (an odd width / height with overlap 0: VapourSynth
 raises there); every other geometry CropAbs refuses -- an overlap >= the base tile, a negative overlap -- is refused with HAVCError.
 
@@ -1236,6 +1244,71 @@ def HAVC_rgb_denoise(clip=None, denoise_levels=(0.4, 0.3), rgb_factors=(0.95, 1.
     tweak.check_clip(tuple(clip.shape), clip.dtype if isinstance(clip, np.ndarray) else np.uint8, "HAVC_rgb_denoise", False)
     return _equalize_clip(clip, device_index, method=0, strength=denoise_levels[1], luma_blend=False, range_tv=True, range_tv_tables=True,
                           balance=(denoise_levels[0], [rgb_factors[0], rgb_factors[1], rgb_factors[2]]))
+
+
+# ---- HAVC_TimeCube / HAVC_clip_overlay (vsdeoldify/__init__.py:2995-3026, 3029-3148) ----------------------------------------------------------------------
+def HAVC_TimeCube(clip, strength=1.0, lut_effect=0, factors=None, *, lut_dir=None, cube=None, device_index=0):
+    """vsdeoldify/__init__.py:2995-3026 -> vs_timecube (vsslib/vsplugins.py:325-378): the 3D LUT of `lut_effect` (0..11: the twelve .cube files under
+    <lut_dir>/color/), vs_tweak with the effect's hue / sat / bright / cont / gamma (or `factors`, those five in that order), then a merge with the input by
+    `strength`: std.Merge, or for effect 8 ChromaBoundAdaptiveMerge (combine_models method 7, cmc_p [0.15, True, 25, 25]).  strength 0 returns the clip itself,
+    strength 1 skips the merge.  Keyword-only extras of this library: lut_dir (default: the environment variable HAVC_LUT_DIR), and cube -- a path or a
+    timecube.Cube that replaces the file lookup while lut_effect still selects the factors and the merge.  The timecube.Cube plugin is a stand-in with one
+    written definition (timecube.py says what is pinned and what is not); the kernel equals it byte for byte.  A LUT file that is not there raises HAVCError
+    (the reference logs and carries on un-graded).  Per call: the LUT (two launches), havc_tweak_clip (two per chunk of frames; not with neutral factors), the
+    merge.  With a tweak the frame needs an even width and height; with neutral factors (0, 1, 0, 1, 1) any size passes.  A frame or a clip; ndarray in ->
+    ndarray out; DeviceImage in -> DeviceImage out (nothing is read back)."""
+    from . import timecube, tweak
+    if not _is_clip(clip):
+        raise HAVCError("HAVC_TimeCube: this is not a clip")
+    tweak.check_clip(tuple(clip.shape), clip.dtype if isinstance(clip, np.ndarray) else np.uint8, "HAVC_TimeCube", False)
+    if lut_dir is None:
+        lut_dir = os.environ.get("HAVC_LUT_DIR") or None
+    plan = timecube.timecube_plan(strength, lut_effect, factors, lut_dir, cube)
+    if plan["identity"]:                                                                          # vsplugins.py:327-328
+        return clip
+    tw = plan["tweak"]
+    if not tw["gamma"] > 0:
+        raise HAVCError(f"HAVC_TimeCube: gamma = {tw['gamma']}: std.Levels needs gamma > 0")
+    tweak_plan = tweak.tweak_plan(**tw)
+    if tweak_plan is not None:
+        tweak.check_clip(tuple(clip.shape), np.uint8, "HAVC_TimeCube", True)
+    lut = timecube.load_cube(plan, cube)
+    ctx = clip.ctx if is_device(clip) else get_context(device_index)
+    new = timecube.lut3d_np(ctx, clip, lut)
+    if tweak_plan is not None:
+        new = tweak.tweak_np(ctx, new, tweak_plan)
+    if plan["merge"] is None:
+        return new
+    shape = tuple(clip.shape)
+    as4 = (lambda x: x.reshaped((1,) + shape) if len(shape) == 3 else x) if is_device(clip) else (lambda x: x.reshape((-1,) + shape[-3:]))
+    a, b = as4(clip if is_device(clip) else np.ascontiguousarray(clip)), as4(new)
+    if plan["merge"][0] == "combine_models":
+        kw = plan["merge"][1]
+        out = combine_models(a, b, kw["method"], kw["w"], cmc_p=kw["cmc_p"], device_index=device_index)
+    else:
+        out = combine_models(a, b, 2, plan["merge"][1], device_index=device_index)                # vs.core.std.Merge = simple_merge
+    return out.reshaped(shape) if is_device(out) else out.reshape(shape)
+
+
+def HAVC_clip_overlay(base, overlay, x=0, y=0, mask=None, opacity=1.0, mode='normal', planes=None, mask_first_plane=True, *, device_index=0):
+    """vsdeoldify/__init__.py:3029-3148 on RGB24 clips: `overlay` ([n, h, w, 3], or one frame [h, w, 3] that is repeated) is put on `base` [n, H, W, 3] with its
+    top left corner at (x, y), either sign; the result has the base's shape.  mode: normal, addition, average, difference, divide, exclusion, multiply, overlay,
+    subtract.  mask: uint8, the overlay's height and width, gray [n, h, w] or three planes [n, h, w, 3] (plane 0 serves all planes with mask_first_plane), as
+    many frames as the overlay; where it is darker the overlay is more transparent.  opacity (clamped to [0, 1]) multiplies the mask.  planes: None (all), an
+    int or a list: the others are the base's.  An overlay entirely outside the base returns a copy of the base.  The native filters underneath are a stand-in
+    with one written definition (overlay.py); the kernel equals it byte for byte.  One launch; nothing is cropped, padded or read back.  The base decides the
+    kind of the result: ndarray -> ndarray, DeviceImage -> DeviceImage; overlay and mask may be of either kind."""
+    from . import overlay as ov
+    if not (_is_clip(base) and _is_clip(overlay)):
+        raise HAVCError('mask_overlay: this is not a clip')
+    if mask is not None and not _is_clip(mask):
+        raise HAVCError('mask_overlay: mask is not a clip')
+    for c in (base, overlay, mask):
+        if isinstance(c, np.ndarray) and c.dtype != np.uint8:
+            raise HAVCError("HAVC: only RGB24 clips (uint8 [n, h, w, 3]) are supported")
+    plan = ov.overlay_plan(base.shape, overlay.shape, None if mask is None else mask.shape, x, y, opacity, mode, planes, mask_first_plane)
+    ctx = base.ctx if is_device(base) else get_context(device_index)
+    return ov.overlay_np(ctx, base, overlay, mask, plan)
 
 
 # ---- HAVC_DeepRemaster (vsdeoldify/__init__.py:2689-2735 -> remaster/__init__.py:203-307 vs_remaster_colorize) ----------------------------------------
