@@ -22,7 +22,8 @@ int run_op(havc_net* n, const havc_op& op, int batch) {
     };
     if (timed) if (int rc = open_tag_pair()) return rc;
     const bool precise = op.flags & HAVC_F_PRECISE;         // fast / precise twins with one parameter list: pick the function, write the call once
-    // Dense-frame ops (MAXPOOL, BLUR_RESIZE, AFFINE, COPY_CH, PREP_RGB8, fast ATTENTION): their kernels place frame b at b x rows x pitch.  That is the
+    // Dense-frame ops (MAXPOOL, BLUR_RESIZE, AFFINE, COPY_CH, PREP_RGB8, fast ATTENTION, SUBSAMPLE2, PROJ2, DWCONV7, DWCONV7_LN, SHUF4_BLUR_AB, LAYERNORM,
+    // PIXSHUF4_BLUR): their kernels place frame b at b x rows x pitch.  That is the
     // buffer's own frame only where the view fills it; a view that covers part of its buffer's frame (the h x w patch rows of a token buffer whose
     // frame also holds a class row) runs one launch per frame, each pointer advanced by its buffer's own frame size -- as the conv op does.
     auto fills = [&](int id, uint64_t elems) { return (uint64_t)n->bufdesc[id].elems_per_frame == elems; };
@@ -276,17 +277,20 @@ int run_op(havc_net* n, const havc_op& op, int batch) {
             });
             break;
         case HAVC_OP_SUBSAMPLE2:
-            e = (precise ? launch_subsample2_p : launch_subsample2)((const half_t*)bufptr(n, op.src), (half_t*)bufptr(n, op.dst), batch, op.Ho, op.Wo, op.Hi, op.Wi,
-                                                                    op.Ci, op.src_cpitch, op.src_coff, op.dst_cpitch, op.dst_coff, s);
+            e = by_frame(fills(op.src, src_rows * op.src_cpitch) && fills(op.dst, dst_rows * op.dst_cpitch), [&](int f, int nb) {
+                return (precise ? launch_subsample2_p : launch_subsample2)((const half_t*)frame_at(op.src, f), (half_t*)frame_at(op.dst, f), nb, op.Ho, op.Wo, op.Hi,
+                                                                           op.Wi, op.Ci, op.src_cpitch, op.src_coff, op.dst_cpitch, op.dst_coff, s);
+            });
             break;
         case HAVC_OP_PROJ2:
-            if (op.flags & HAVC_F_PRECISE) {
-                e = launch_proj2_p((const half_t*)bufptr(n, op.src), op.src_cpitch, op.src_coff, op.Ci, wptr<float>(n, op.w_off), wptr<float>(n, op.bias_off),
-                                   op.flags & 3, op.f0, (float*)bufptr(n, op.dst), (int64_t)batch * op.Hi * op.Wi, s);
-                break;
-            }
-            e = launch_proj2((const half_t*)bufptr(n, op.src), op.src_cpitch, op.src_coff, op.Ci, wptr<float>(n, op.w_off),
-                             wptr<float>(n, op.bias_off), op.flags, op.f0, (float*)bufptr(n, op.dst), (int64_t)batch * op.Hi * op.Wi, s);
+            if (!precise && (op.w_off < 0 || op.Ci < 1 || op.Ci > 512)) return fail(c, HAVC_E_INVALID, "proj2 op: weights, 1 <= C <= 512 (eight channels per lane)");
+            e = by_frame(fills(op.src, src_rows * op.src_cpitch) && fills(op.dst, src_rows * 2), [&](int f, int nb) {
+                if (precise)
+                    return launch_proj2_p((const half_t*)frame_at(op.src, f), op.src_cpitch, op.src_coff, op.Ci, wptr<float>(n, op.w_off), wptr<float>(n, op.bias_off),
+                                          op.flags & 3, op.f0, (float*)frame_at(op.dst, f), (int64_t)nb * op.Hi * op.Wi, s);
+                return launch_proj2((const half_t*)frame_at(op.src, f), op.src_cpitch, op.src_coff, op.Ci, wptr<float>(n, op.w_off),
+                                    wptr<float>(n, op.bias_off), op.flags, op.f0, (float*)frame_at(op.dst, f), (int64_t)nb * op.Hi * op.Wi, s);
+            });
             break;
         case HAVC_OP_BILINEAR2:
             e = launch_bilinear2((const float*)bufptr(n, op.src), (float*)bufptr(n, op.dst), batch, op.Hi, op.Wi, op.Ho, op.Wo, op.f0, s);
@@ -297,27 +301,28 @@ int run_op(havc_net* n, const havc_op& op, int batch) {
             break;
         case HAVC_OP_DWCONV7:
             if (op.w_off < 0 || (op.Ci & 7)) return fail(c, HAVC_E_INVALID, "dwconv7 op: weights / channel count");
-            if (op.flags & HAVC_F_PRECISE) {                   // fp32 weights [49][Kc]
-                e = launch_dwconv7_p((const half_t*)bufptr(n, op.src), wptr<float>(n, op.w_off), wptr<float>(n, op.bias_off), (half_t*)bufptr(n, op.dst), batch,
-                                     op.Hi, op.Wi, op.Ci, op.src_cpitch, op.src_coff, op.dst_cpitch, op.dst_coff, op.Kc, s);
-                break;
-            }
-            e = launch_dwconv7((const half_t*)bufptr(n, op.src), wptr<half_t>(n, op.w_off), wptr<float>(n, op.bias_off), (half_t*)bufptr(n, op.dst),
-                               batch, op.Hi, op.Wi, op.Ci, op.src_cpitch, op.src_coff, op.dst_cpitch, op.dst_coff, op.Kc, s);
+            e = by_frame(fills(op.src, src_rows * op.src_cpitch) && fills(op.dst, src_rows * op.dst_cpitch), [&](int f, int nb) {
+                if (precise)                                       // fp32 weights [49][Kc]
+                    return launch_dwconv7_p((const half_t*)frame_at(op.src, f), wptr<float>(n, op.w_off), wptr<float>(n, op.bias_off), (half_t*)frame_at(op.dst, f),
+                                            nb, op.Hi, op.Wi, op.Ci, op.src_cpitch, op.src_coff, op.dst_cpitch, op.dst_coff, op.Kc, s);
+                return launch_dwconv7((const half_t*)frame_at(op.src, f), wptr<half_t>(n, op.w_off), wptr<float>(n, op.bias_off), (half_t*)frame_at(op.dst, f),
+                                      nb, op.Hi, op.Wi, op.Ci, op.src_cpitch, op.src_coff, op.dst_cpitch, op.dst_coff, op.Kc, s);
+            });
             break;
         case HAVC_OP_DWCONV7_LN:
             if (op.w_off < 0 || op.scale_off < 0 || op.shift_off < 0 || !dwconv7_ln_supported(op.Ci))
                 return fail(c, HAVC_E_INVALID, "dwconv7+layernorm op: weights / gamma / beta / channel count");
-            if (op.flags & HAVC_F_PRECISE) {                       // pair tensors, fp32 weights (round 6)
-                if (!dwconv7_ln_p_supported(op.Ci)) return fail(c, HAVC_E_INVALID, "dwconv7+layernorm op: the precise form exists for 192 / 384 / 768 channels");
-                e = launch_dwconv7_ln_p((const half_t*)bufptr(n, op.src), wptr<float>(n, op.w_off), wptr<float>(n, op.bias_off), wptr<float>(n, op.scale_off),
-                                        wptr<float>(n, op.shift_off), op.f0, (half_t*)bufptr(n, op.dst), batch, op.Hi, op.Wi, op.Ci, op.src_cpitch,
-                                        op.src_coff, op.dst_cpitch, op.dst_coff, op.Kc, s);
-                break;
-            }
-            e = launch_dwconv7_ln((const half_t*)bufptr(n, op.src), wptr<half_t>(n, op.w_off), wptr<float>(n, op.bias_off), wptr<float>(n, op.scale_off),
-                                  wptr<float>(n, op.shift_off), op.f0, (half_t*)bufptr(n, op.dst), batch, op.Hi, op.Wi, op.Ci, op.src_cpitch,
-                                  op.src_coff, op.dst_cpitch, op.dst_coff, op.Kc, s);
+            if (precise && !dwconv7_ln_p_supported(op.Ci))         // pair tensors, fp32 weights (round 6)
+                return fail(c, HAVC_E_INVALID, "dwconv7+layernorm op: the precise form exists for 192 / 384 / 768 channels");
+            e = by_frame(fills(op.src, src_rows * op.src_cpitch) && fills(op.dst, src_rows * op.dst_cpitch), [&](int f, int nb) {
+                if (precise)
+                    return launch_dwconv7_ln_p((const half_t*)frame_at(op.src, f), wptr<float>(n, op.w_off), wptr<float>(n, op.bias_off), wptr<float>(n, op.scale_off),
+                                               wptr<float>(n, op.shift_off), op.f0, (half_t*)frame_at(op.dst, f), nb, op.Hi, op.Wi, op.Ci, op.src_cpitch,
+                                               op.src_coff, op.dst_cpitch, op.dst_coff, op.Kc, s);
+                return launch_dwconv7_ln((const half_t*)frame_at(op.src, f), wptr<half_t>(n, op.w_off), wptr<float>(n, op.bias_off), wptr<float>(n, op.scale_off),
+                                         wptr<float>(n, op.shift_off), op.f0, (half_t*)frame_at(op.dst, f), nb, op.Hi, op.Wi, op.Ci, op.src_cpitch,
+                                         op.src_coff, op.dst_cpitch, op.dst_coff, op.Kc, s);
+            });
             break;
         case HAVC_OP_FOLD_QUERIES:
             if (op.w_off < 0 || op.Ho < 1 || op.Ho > op.Kc || op.Ho > op.Wi || (op.Ci & 7) || n->bufdesc[op.dst].elem_bytes != 4 ||
@@ -332,9 +337,11 @@ int run_op(havc_net* n, const havc_op& op, int batch) {
                 if (op.w_off < 0 || op.bias_off < 0 || op.src2 < 0 || n->bufdesc[op.src].elem_bytes != 4 ||
                     (uint64_t)n->bufdesc[op.src].elems_per_frame < (uint64_t)op.Hi * op.Wi * 32)
                     return fail(c, HAVC_E_INVALID, "shuffle+blur(ab) op, precise: weights, image view, fp32 [Hi*Wi][16][2] source");
-                e = launch_shuf4_blur_ab_p((const float*)bufptr(n, op.src), (const half_t*)bufptr(n, op.src2), op.res_cpitch, op.res_coff,
-                                           wptr<float>(n, op.w_off), wptr<float>(n, op.bias_off), (half_t*)bufptr(n, op.dst), op.dst_cpitch, op.dst_coff,
-                                           batch, op.Hi, op.Wi, s);
+                e = by_frame(fills(op.src, src_rows * 32) && fills(op.src2, dst_rows * op.res_cpitch) && fills(op.dst, dst_rows * op.dst_cpitch), [&](int f, int nb) {
+                    return launch_shuf4_blur_ab_p((const float*)frame_at(op.src, f), (const half_t*)frame_at(op.src2, f), op.res_cpitch, op.res_coff,
+                                                  wptr<float>(n, op.w_off), wptr<float>(n, op.bias_off), (half_t*)frame_at(op.dst, f), op.dst_cpitch, op.dst_coff,
+                                                  nb, op.Hi, op.Wi, s);
+                });
                 break;
             }
             if (op.flags & HAVC_F_PRECISE) {
@@ -350,26 +357,30 @@ int run_op(havc_net* n, const havc_op& op, int batch) {
             if (op.w_off < 0 || op.bias_off < 0 || op.src2 < 0 || n->bufdesc[op.src].elem_bytes != 4 ||
                 (uint64_t)n->bufdesc[op.src].elems_per_frame < (uint64_t)op.Hi * op.Wi * 32)
                 return fail(c, HAVC_E_INVALID, "shuffle+blur(ab) op: weights, image view, fp32 [Hi*Wi][16][2] source");
-            e = launch_shuf4_blur_ab((const float*)bufptr(n, op.src), (const half_t*)bufptr(n, op.src2), op.res_cpitch, op.res_coff,
-                                     wptr<float>(n, op.w_off), wptr<float>(n, op.bias_off), (half_t*)bufptr(n, op.dst), op.dst_cpitch, op.dst_coff,
-                                     batch, op.Hi, op.Wi, s);
+            e = by_frame(fills(op.src, src_rows * 32) && fills(op.src2, dst_rows * op.res_cpitch) && fills(op.dst, dst_rows * op.dst_cpitch), [&](int f, int nb) {
+                return launch_shuf4_blur_ab((const float*)frame_at(op.src, f), (const half_t*)frame_at(op.src2, f), op.res_cpitch, op.res_coff,
+                                            wptr<float>(n, op.w_off), wptr<float>(n, op.bias_off), (half_t*)frame_at(op.dst, f), op.dst_cpitch, op.dst_coff,
+                                            nb, op.Hi, op.Wi, s);
+            });
             break;
         case HAVC_OP_LAYERNORM:
             if (op.scale_off < 0 || op.shift_off < 0) return fail(c, HAVC_E_INVALID, "layernorm op: gamma / beta");
-            if (op.flags & HAVC_F_PRECISE) {
-                e = launch_layernorm_p((const half_t*)bufptr(n, op.src), (half_t*)bufptr(n, op.dst), wptr<float>(n, op.scale_off), wptr<float>(n, op.shift_off),
-                                       op.f0, (int64_t)batch * op.Hi * op.Wi, op.Ci, op.src_cpitch, op.src_coff, op.dst_cpitch, op.dst_coff,
-                                       (op.flags & HAVC_F_RELU_POST) ? 1 : 0, s);
-                break;
-            }
-            e = launch_layernorm_c((const half_t*)bufptr(n, op.src), (half_t*)bufptr(n, op.dst), wptr<float>(n, op.scale_off),
-                                   wptr<float>(n, op.shift_off), op.f0, (int64_t)batch * op.Hi * op.Wi, op.Ci, op.src_cpitch, op.src_coff,
-                                   op.dst_cpitch, op.dst_coff, s, (op.flags & HAVC_F_RELU_POST) ? 1 : 0);
+            if (!precise && (op.Ci < 1 || op.Ci > 2048)) return fail(c, HAVC_E_INVALID, "layernorm op: 1 <= C <= 2048 (four 8-channel chunks per lane, 64 lanes)");
+            e = by_frame(fills(op.src, src_rows * op.src_cpitch) && fills(op.dst, src_rows * op.dst_cpitch), [&](int f, int nb) {
+                if (precise)
+                    return launch_layernorm_p((const half_t*)frame_at(op.src, f), (half_t*)frame_at(op.dst, f), wptr<float>(n, op.scale_off),
+                                              wptr<float>(n, op.shift_off), op.f0, (int64_t)nb * op.Hi * op.Wi, op.Ci, op.src_cpitch, op.src_coff, op.dst_cpitch,
+                                              op.dst_coff, (op.flags & HAVC_F_RELU_POST) ? 1 : 0, s);
+                return launch_layernorm_c((const half_t*)frame_at(op.src, f), (half_t*)frame_at(op.dst, f), wptr<float>(n, op.scale_off),
+                                          wptr<float>(n, op.shift_off), op.f0, (int64_t)nb * op.Hi * op.Wi, op.Ci, op.src_cpitch, op.src_coff,
+                                          op.dst_cpitch, op.dst_coff, s, (op.flags & HAVC_F_RELU_POST) ? 1 : 0);
+            });
             break;
         case HAVC_OP_MHA:
             if (op.src2 < 0 || op.Ci != op.kh * 32) return fail(c, HAVC_E_INVALID, "mha op: K/V buffer, head dim 32");
-            if (!precise && op.aux1 >= 0 && op.aux1 < (int)n->bufs.size() && n->bufdesc[op.aux1].elem_bytes == 4) {
-                // keys split over blocks (K / V staged in LDS once per block), partial softmax states in the fp32 buffer aux1
+            if (!precise && op.Hi <= 128 && op.aux1 >= 0 && op.aux1 < (int)n->bufs.size() && n->bufdesc[op.aux1].elem_bytes == 4) {
+                // keys split over blocks (K / V staged in LDS once per block), partial softmax states in the fp32 buffer aux1.  A block of the split kernel
+                // holds 128 queries (four waves x two 16-query fragments): more queries run on the one-wave-per-query kernel below, which has no such limit
                 if ((size_t)n->bufdesc[op.aux1].elems_per_frame < (size_t)op.kh * mha32_nsplit(op.Ho) * op.Hi * 34)
                     return fail(c, HAVC_E_INVALID, "mha op: partial-state buffer too small");
                 e = launch_mha32_split((const half_t*)bufptr(n, op.src), op.src_cpitch, op.src_coff, op.Wi, (const half_t*)bufptr(n, op.src2),
@@ -383,8 +394,10 @@ int run_op(havc_net* n, const havc_op& op, int batch) {
                                                           batch, op.kh, op.Hi, op.Ho, op.f0, s);
             break;
         case HAVC_OP_PIXSHUF4_BLUR:
-            e = launch_pixshuf4_blur((const half_t*)bufptr(n, op.src), (half_t*)bufptr(n, op.dst), batch, op.Hi, op.Wi, op.Co, op.src_cpitch,
-                                     op.src_coff, op.dst_cpitch, op.dst_coff, s);
+            e = by_frame(fills(op.src, src_rows * op.src_cpitch) && fills(op.dst, dst_rows * op.dst_cpitch), [&](int f, int nb) {
+                return launch_pixshuf4_blur((const half_t*)frame_at(op.src, f), (half_t*)frame_at(op.dst, f), nb, op.Hi, op.Wi, op.Co, op.src_cpitch,
+                                            op.src_coff, op.dst_cpitch, op.dst_coff, s);
+            });
             break;
         case HAVC_OP_PREP_DDCOLOR:
             e = launch_prep_ddcolor((const uint8_t*)bufptr(n, op.src), (half_t*)bufptr(n, op.dst), op.dst_cpitch, op.dst_coff,
