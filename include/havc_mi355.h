@@ -922,6 +922,10 @@ int havc_debug_stream_jitter(int seed, int max_us);
  * by the Makefile.  The shared object is git-ignored and travels prebuilt to the GPU box: tests/test_host_logic.py compares this with the tree, so a stale binary fails a
  * CPU test wherever the suite runs (round 6; no reference counterpart). */
 const char* havc_build_stamp(void);
+/* The conv kernels divide pixel indices by launch constants (Ho * Wo, Wo, the PS_BLUR tile counts) with a multiplier and a shift computed on the host
+ * (csrc/conv_common.h: fast_div_make, fast_div).  This runs the SAME inline function on the host: quotients[i] = what the kernels compute for
+ * dividends[i] / divisor.  Exact for divisor in [1, 2^31] and dividends below 2^31 (tests/test_conv_fast_div.py).  Host only, no context needed. */
+int havc_conv_fast_div(uint32_t divisor, const uint32_t* dividends, uint32_t* quotients, int64_t count);
 
 /* timing of the dominant kernel for bench.py's roofline object: average duration (ms) and launch count
  * of HAVC_OP_CONV ops with the given tag over the launches since havc_reset_stats (HIP events on the

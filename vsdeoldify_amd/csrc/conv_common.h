@@ -2,6 +2,7 @@
 #pragma once
 #include "kernels.h"
 #include "../../include/havc_mi355.h"
+#include <algorithm>
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
@@ -23,10 +24,37 @@ __device__ __forceinline__ float gelu_erf(float v) {
     return v * __builtin_amdgcn_rcpf(1.0f + e);
 }
 
-// output pixel index of GEMM row m (identity unless the conv scatters with an output step: ConvTranspose parity convs)
+// ---- division by a launch constant without a division ----
+// The kernels' pixel index math divides by Ho * Wo, Wo and the PS_BLUR tile counts, per lane and per DMA piece (~1 800 clocks of a block's prologue as
+// integer divisions).  For d > 1 take l = ceil(log2 d) and mul = ceil(2^(31 + l) / d): 2^(l-1) < d <= 2^l puts mul in [2^31, 2^32), and
+// mul * d = 2^(31 + l) + e with 0 <= e < d <= 2^l, so n * mul / 2^(31 + l) = n / d + n e / (d 2^(31 + l)) with an excess below 1 / d for every
+// n < 2^31: the floor is n / d exactly.  In 32-bit terms: the high half of n * mul, shifted right by l - 1.  d == 1 has no such multiplier (it would be
+// 2^32) and is marked by mul == 0.  The host computes (mul, sh) where it fills ConvArgs; host and device divide through this one function.
+__host__ __device__ __forceinline__ unsigned fast_div(unsigned n, const FastDiv d) {
+    return d.mul ? (unsigned)(((uint64_t)n * d.mul) >> 32) >> d.sh : n;
+}
+inline FastDiv fast_div_make(unsigned d) {         // d in [1, 2^31]
+    if (d <= 1) return FastDiv{0u, 0u};
+    unsigned l = 0;
+    while ((1ull << l) < d) ++l;
+    const uint64_t pw = 1ull << (31 + l);
+    return FastDiv{(unsigned)((pw + d - 1) / d), l - 1};
+}
+// the divisors of a conv launch (call when Ho, Wo, tiles_y, tiles_x stand)
+inline void conv_set_divisors(ConvArgs& a) {
+    a.fd_howo = fast_div_make((unsigned)std::max(a.Ho * a.Wo, 1));
+    a.fd_wo = fast_div_make((unsigned)std::max(a.Wo, 1));
+    a.fd_tt = fast_div_make((unsigned)std::max(a.tiles_y * a.tiles_x, 1));
+    a.fd_tx = fast_div_make((unsigned)std::max(a.tiles_x, 1));
+}
+
+// output pixel index of GEMM row m (identity unless the conv scatters with an output step: ConvTranspose parity convs).  FD: divide with fast_div (the fast
+// pipelined kernels); the register-staged and the precise kernels keep `/` (fast_div's operands pushed the precise 128 x 272 register tile into scratch)
+template <bool FD = false>
 __device__ __forceinline__ int64_t out_pixel(const ConvArgs& p, int m, int HoWo) {
     if (p.oss == 1) return m;
-    const int b = m / HoWo, rem = m - b * HoWo, ho = rem / p.Wo, wo = rem - ho * p.Wo;
+    const int b = FD ? (int)fast_div((unsigned)m, p.fd_howo) : m / HoWo, rem = m - b * HoWo;
+    const int ho = FD ? (int)fast_div((unsigned)rem, p.fd_wo) : rem / p.Wo, wo = rem - ho * p.Wo;
     return ((int64_t)(b * p.Ho * p.oss + ho * p.oss + p.ooy)) * (p.Wo * p.oss) + wo * p.oss + p.oox;
 }
 

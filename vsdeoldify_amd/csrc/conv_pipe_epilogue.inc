@@ -480,7 +480,7 @@
 #pragma unroll
         for (int mi = 0; mi < FM; ++mi) {
             const int mf = gm(wm * (FM * 16) + mi * 16);    // a 16-pixel fragment lies in one frame (Ho * Wo % 16 == 0)
-            const int fb = mf < p.M ? mf / HoWo : 0;
+            const int fb = mf < p.M ? (int)fast_div((unsigned)mf, p.fd_howo) : 0;
             if (fb != fb_prev) {
                 fb_prev = fb;
 #pragma unroll
@@ -571,7 +571,7 @@
             // rounding of the shuffled values and the same summation order as elementwise.hip blur_resize_kernel.
             __syncthreads();
             const int tile = m0 / BM, tt = p.tiles_y * p.tiles_x;
-            const int b = tile / tt, t = tile - b * tt, ty = t / p.tiles_x, tx = t - ty * p.tiles_x;
+            const int b = (int)fast_div((unsigned)tile, p.fd_tt), t = tile - b * tt, ty = (int)fast_div((unsigned)t, p.fd_tx), tx = t - ty * p.tiles_x;
             const int h0 = ty * 15 - 1, w0 = tx * 15 - 1, H2 = 2 * p.Ho, W2 = 2 * p.Wo;
             half_t* y = reinterpret_cast<half_t*>(p.y) + p.y_coff + (n0 >> 2);          // 64 output channels per 256-column tile
             // Thread (row Yl of the 30 x 30 output tile, half xh of the row, 16-byte channel chunk ch) walks 15 consecutive output
@@ -652,8 +652,8 @@
                 if (eflags & HAVC_F_OUT_PIXSHUF) {
                     const int q = n / p.Co, cc = n - q * p.Co;
                     if (q >= 4) continue;
-                    const int b = m / HoWo, rem = m - b * HoWo, ho = rem / p.Wo, wo = rem - ho * p.Wo;
-                    off = ((int64_t)(b * 2 * p.Ho + 2 * ho + (q >> 1)) * (2 * p.Wo) + 2 * wo + (q & 1)) * p.y_cpitch + p.y_coff + cc;
+                    const int b = (int)fast_div((unsigned)m, p.fd_howo), rem = m - b * HoWo, ho = (int)fast_div((unsigned)rem, p.fd_wo), wo = rem - ho * p.Wo;
+                    off =((int64_t)(b * 2 * p.Ho + 2 * ho + (q >> 1)) * (2 * p.Wo) + 2 * wo + (q & 1)) * p.y_cpitch + p.y_coff + cc;
                 } else {
                     if (n >= p.Co) continue;
                     off = opix(m) * p.y_cpitch + p.y_coff + n;

@@ -119,8 +119,8 @@ __global__ void __launch_bounds__(WM* WN * 64, HAVC_PIPE_WPE) conv_pipe_kernel(c
     const int2* kt_lane = p.ktab + c;                  // this lane's chunk of every stage: kt_lane[kt * 8]
 
     // The WEIGHT pieces of the first stage and the first K-table entry go out before anything else (round 4): they need nothing but n0, and the
-    // pixel index math below (integer divisions: ~1 800 clocks per block on the phase stamps of tools/conv_timeline.py) then runs under their
-    // latency instead of in front of it.
+    // pixel index math below then runs under their latency instead of in front of it.  (Its integer divisions were ~1 800 clocks per block on the
+    // phase stamps of tools/conv_timeline.py; they are a multiply-high and a shift each now: fast_div, profiles/conv_fixed_cost.txt.)
     unsigned b_voff[B_IT];
 #pragma unroll
     for (int it = 0; it < B_IT; ++it) {
@@ -140,15 +140,15 @@ __global__ void __launch_bounds__(WM* WN * 64, HAVC_PIPE_WPE) conv_pipe_kernel(c
         const int m = m0 + row;
         const bool ok = m < p.M;
         const int mm = ok ? m : 0;
-        int b = mm / HoWo;
+        int b = (int)fast_div((unsigned)mm, p.fd_howo);         // multiply-high + shift: the divisors are launch constants (conv_common.h)
         const int rem = mm - b * HoWo;
-        int ho = rem / p.Wo;
+        int ho = (int)fast_div((unsigned)rem, p.fd_wo);
         int wo = rem - ho * p.Wo;
         if ((EF >= 0 ? EF : p.flags) & HAVC_F_PS_BLUR) {   // GEMM rows = 16x16 pixel tiles, origin (15 ty - 1, 15 tx - 1), clamped (a compile-time fact when EF is fixed:
                                                            // round 6, the tile-index divisions leave the prologue of every other layer kind -- tail conv 5.33 -> 5.25 ms, same box)
             const int tile = m0 / BM, tt = p.tiles_y * p.tiles_x;
-            b = tile / tt;
-            const int t = tile - b * tt, ty = t / p.tiles_x, tx = t - ty * p.tiles_x;
+            b = (int)fast_div((unsigned)tile, p.fd_tt);
+            const int t = tile - b * tt, ty = (int)fast_div((unsigned)t, p.fd_tx), tx = t - ty * p.tiles_x;
             ho = min(max(ty * 15 - 1 + (row >> 4), 0), p.Ho - 1);
             wo = min(max(tx * 15 - 1 + (row & 15), 0), p.Wo - 1);
         }
@@ -224,15 +224,19 @@ __global__ void __launch_bounds__(WM* WN * 64, HAVC_PIPE_WPE) conv_pipe_kernel(c
     // gets the rest of this stage plus most of the next one to land instead of racing the next barrier, and (b) stage
     // kt+1's data is complete, so its first fragments are fetched under the MFMAs of steps NS-2, NS-1 -- the MFMA
     // pipe no longer drains at a stage boundary.
-    auto stage = [&](int kt, auto lvl_tag) {
+    // skip2 (wave-uniform, last stage only): chunks 4..7 of the stage are pad entries of the K table (p.k_half_empty: the 259-channel convs' remainder
+    // segment, 9 real chunks padded to 16) -- the stage runs its first FM steps only: ONE scalar branch over the second half's steps.  The skipped MFMAs
+    // would add +0 products to accumulators that started at +0 and therefore never hold -0: every bit stays.  (Two instantiations of the last stage, a
+    // full and a half one, made the allocator spill 120 - 190 registers in the 256-register tiles; the branch over half a stage costs none.)
+    auto stage = [&](int kt, auto lvl_tag, const bool skip2) {
         constexpr int LVL = ABL == 10 ? 0 : ABL == 1 ? (decltype(lvl_tag)::value ? 1 : 0) : decltype(lvl_tag)::value;
+        constexpr bool MAY_SKIP = decltype(lvl_tag)::value == 0 && ABL != 30;       // (the precise kernels keep today's code)
         constexpr bool RD = ABL != 10;
         constexpr bool DMA_ON = ABL != 1;
         const char* cur = smem + (kt & 1) * G::STAGE_BYTES;
         char* nxt = smem + ((kt & 1) ^ 1) * G::STAGE_BYTES;
         int2 e_n2 = e_nx;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {                 // step s: K half s / FM, pixel fragment s % FM
+        auto step = [&](const int s) __attribute__((always_inline)) {      // step s: K half s / FM, pixel fragment s % FM
             const int ks = s / FM, mi = s % FM;
             if (s == 0 && LVL == 2) e_n2 = kt_lane[(kt + 2) * 8];             // K table entry of stage kt+2
             {                                          // (1) pixel fragment two steps ahead (next stage's at the end)
@@ -275,6 +279,12 @@ __global__ void __launch_bounds__(WM* WN * 64, HAVC_PIPE_WPE) conv_pipe_kernel(c
             if (EXTRA && mi < 2)                       // extra column fragment x this wave's pixel fragments PF(0), PF(1) = 2 wn, 2 wn + 1: static steps
                 accx[mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xb[ks], a, accx[mi], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
+        };
+#pragma unroll
+        for (int s = 0; s < FM; ++s) step(s);
+        if (!(MAY_SKIP && skip2)) {
+#pragma unroll
+            for (int s = FM; s < NS; ++s) step(s);
         }
         e_nx = e_n2;
     };
@@ -283,9 +293,9 @@ __global__ void __launch_bounds__(WM* WN * 64, HAVC_PIPE_WPE) conv_pipe_kernel(c
     // 5.99 -> 5.83 ms on the tail conv (interleaved same-box A/B, profiles/r3_conv_experiments.txt).  Scheduling only: same bytes.
     if (NW == 8 && p.prio && wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
     int kt = kt0;
-    for (; kt + 2 < kt1; ++kt) stage(kt, std::integral_constant<int, 2>{});
-    if (kt1 - kt0 >= 2) { stage(kt, std::integral_constant<int, 1>{}); ++kt; }
-    stage(kt, std::integral_constant<int, 0>{});
+    for (; kt + 2 < kt1; ++kt) stage(kt, std::integral_constant<int, 2>{}, false);
+    if (kt1 - kt0 >= 2) { stage(kt, std::integral_constant<int, 1>{}, false); ++kt; }
+    stage(kt, std::integral_constant<int, 0>{}, p.k_half_empty && kt1 == KT);       // split-K: only the part that owns the last stage of the K table
     HAVC_STAMP(2);
 
     auto gm = [&](int local_row) -> int { return m0 + local_row; };
@@ -309,7 +319,7 @@ __global__ void __launch_bounds__(WM* WN * 64, HAVC_PIPE_WPE) conv_pipe_kernel(c
     }
     const int eflags = EF >= 0 ? (EF | (p.flags & ~HAVC_EPI_MASK)) : p.flags;
     constexpr bool UNIT_STEP = EF >= 0;                    // the compile-time-flag kernels are launched for out step 1 only
-    auto opix = [&](int m) -> int64_t { return EF >= 0 ? (int64_t)m : out_pixel(p, m, HoWo); };
+    auto opix = [&](int m) -> int64_t { return EF >= 0 ? (int64_t)m : out_pixel<ABL != 30>(p, m, HoWo); };
 #include "conv_pipe_epilogue.inc"
 #undef PF
     if (ABL == 40) {

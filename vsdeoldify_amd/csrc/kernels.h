@@ -5,6 +5,9 @@
 
 typedef _Float16 half_t;
 
+// a launch-constant divisor as multiplier + shift: n / d == fast_div(n, fd) for every 0 <= n < 2^31 (conv_common.h: fast_div_make, fast_div)
+struct FastDiv { unsigned mul, sh; };
+
 struct ConvArgs {
     const half_t* x;       // input NHWC fp16
     const half_t* w;       // packed weights [Npad][Kc][8] fp16
@@ -45,6 +48,9 @@ struct ConvArgs {
     float pscale;          // HAVC_F_PRECISE: the accumulator is this factor away from the convolution (2^-11 x the weight pre-scale, op.f3)
     int ngroup, rband;     // round 6, set by the pipelined launchers (conv_raster): > 0 = column tiles are walked in groups of `ngroup` inside bands of `rband` row tiles,
                            //      so that the weight panels one XCD has in flight fit its 4 MiB L2 (a 768 -> 3072 GEMM cycles 4.7 MB of weights per row tile otherwise)
+    FastDiv fd_howo, fd_wo;    // the pixel index math of the kernels divides by Ho * Wo and Wo, the PS_BLUR kernels by tiles_y * tiles_x and tiles_x: filled with
+    FastDiv fd_tt, fd_tx;      //      the rest of the struct (conv_set_divisors)
+    int k_half_empty;          // 1: chunks 4..7 of the LAST stage of the K table are all pad entries -- the pipelined kernels skip that stage's second K half
 };
 // grouped tile order for GEMMs whose weight matrix does not fit an XCD's L2.  Same bytes: only the block -> tile map changes.  MEASURED AND LEFT OFF (round 6,
 // profiles/r6_raster_group_ab.txt): on ConvNeXt-L's stage-2 pwconv1 (768 -> 3072, 128 frames) it cuts the kernel's HBM-side traffic from 2.13 to 1.76 GB per launch

@@ -1,5 +1,6 @@
 // libhavc_mi355.so runtime, plan executor: packed weights, nets (create / free / bind / run), the per-op dispatch, autotuner, profiler, range check.
 #include "runtime_internal.h"
+#include "conv_common.h"
 
 namespace {
 
@@ -101,6 +102,8 @@ int run_op(havc_net* n, const havc_op& op, int batch) {
             a.C8a = (op.aux1 > 0 && op.aux1 < op.Ci / 8) ? op.aux1 : op.Ci / 8;
             a.f0 = op.f0; a.f1 = op.f1; a.f2 = op.f2;
             a.cfg = op.reserved;
+            conv_set_divisors(a);          // Ho, Wo, tiles_y, tiles_x stand: multiplier + shift of the kernels' index divisions (a few host divisions per op)
+            a.k_half_empty = n->k_half_empty[(size_t)(&op - n->ops.data())];
             { static const int prio = [] { const char* e = getenv("HAVC_SETPRIO"); return e ? atoi(e) != 0 : 1; }(); a.prio = prio; }
             a.splitk = HAVC_F_SPLITK_COUNT(op.flags);
             if (a.splitk == 1) a.splitk = 0;
@@ -646,6 +649,13 @@ void havc_weights_free(havc_weights* w) {
     delete w;
 }
 
+int havc_conv_fast_div(uint32_t divisor, const uint32_t* dividends, uint32_t* quotients, int64_t count) {
+    if (divisor < 1 || divisor > 0x80000000u || count < 0 || (count > 0 && (!dividends || !quotients))) return HAVC_E_INVALID;
+    const FastDiv fd = fast_div_make(divisor);
+    for (int64_t i = 0; i < count; ++i) quotients[i] = fast_div(dividends[i], fd);
+    return HAVC_OK;
+}
+
 int havc_net_create(havc_ctx* c, havc_weights* w, const havc_op* ops, int n_ops, const havc_buf* bufs, int n_bufs,
                     int in_buf, int out_buf, int S, int max_batch, havc_net** out) {
     if (!c || !w || !ops || !bufs || !out || n_ops <= 0 || n_bufs <= 0 || max_batch < 1)
@@ -681,6 +691,7 @@ int havc_net_create(havc_ctx* c, havc_weights* w, const havc_op* ops, int n_ops,
     {
         std::vector<int2> host;
         n->ktab_off.assign(n_ops, -1);
+        n->k_half_empty.assign(n_ops, 0);
         for (int i = 0; i < n_ops; ++i) {
             const havc_op& o = ops[i];
             if (o.type != HAVC_OP_CONV) continue;
@@ -723,6 +734,14 @@ int havc_net_create(havc_ctx* c, havc_weights* w, const havc_op* ops, int n_ops,
             if ((int)(host.size() - start) != o.Kc) {
                 delete n;
                 return fail(c, HAVC_E_INVALID, "net_create: conv op Kc does not match its K layout (Ci, kh, kw, aux1)");
+            }
+            // The last stage (8 chunks) of a K table whose chunks 4..7 are all pad entries: those chunks bring zero pixels against zero-padded weight
+            // columns, and the pipelined kernels skip that K half (the 259-channel convs: a remainder segment of 9 chunks padded to 16).  Left off for
+            // precise ops and for weights that come from an activation buffer (nothing pads those with zeros but the producer).
+            if (o.Kc >= 8 && !(o.Kc & 7) && !(o.flags & (HAVC_F_PRECISE | HAVC_F_W_FROM_BUF))) {
+                bool empty = true;
+                for (int k = 4; k < 8; ++k) empty = empty && (short)(host[start + o.Kc - 8 + k].y & 0xffff) == HAVC_KTAB_PAD_DH;
+                n->k_half_empty[i] = empty;
             }
         }
         if (!host.empty()) {

@@ -159,6 +159,7 @@ struct havc_net {
     int tail_first = -1;                  // index of the first op tagged 1 (exclusive tail), -1 if none
     int2* d_ktab = nullptr;               // all conv K tables, one allocation
     std::vector<int64_t> ktab_off;        // per op: element offset into d_ktab, -1 for non-conv ops
+    std::vector<uint8_t> k_half_empty;    // per op: 1 = chunks 4..7 of the last stage of its K table are all pad entries (ConvArgs::k_half_empty)
     const void* in_override = nullptr;
     void* out_override = nullptr;
     unsigned* d_range = nullptr;          // range check: per op {abs-max bits, -, non-finite count (64 bit)}
