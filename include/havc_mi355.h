@@ -642,6 +642,36 @@ int havc_yuv420_to_rgb(havc_ctx* ctx, const uint8_t* y, const uint8_t* u, const 
 /* the chroma filters of the calls above, on the host (no context, no GPU): out32 = the 8 weights of the vertical 2 : 1 pass, the 8 of the horizontal one,
  * 2 x 4 of the vertical 1 : 2 pass (even output row, odd), 2 x 4 of the horizontal one */
 int havc_tweak_weights(float* out32);
+/* convert_format_RGB24 / restore_format (vsdeoldify/havc_utils.py:57-237) on a clip's own planes: what a decoder hands over and an encoder takes.  The two
+ * resize.Bicubic calls of the reference are zimg's; like the conversions above they are an UNPINNED stand-in whose definition is tests/vformat_util.py (built
+ * on tests/tweak_util.py), and the kernels (csrc/vformat.hip) equal it byte for byte.  The resampler (Mitchell, vertical pass first, centred vertical and left
+ * horizontal siting, mirrored edges), the error diffusion and the float32 discipline are those of havc_tweak_clip; at matrix 1 / full range / 8 bit / 4:2:0 the
+ * bytes are those of havc_yuv420_to_rgb (dither 1) and havc_rgb_to_yuv420 (dither 0).  What this project writes down on top (float32, one rounding each):
+ *   matrix       KR, KB = 0.2126, 0.0722 (1: BT.709), 0.299, 0.114 (5: BT.470BG, 6: SMPTE 170M), 0.2627, 0.0593 (9: BT.2020 NCL); KG = 1 - KR - KB
+ *   to codes     limited, depth b: Y code = Y 219 2^(b-8) + 16 2^(b-8), C code = C 224 2^(b-8) + 2^(b-1);  full: Y (2^b - 1) + 0, C (2^b - 1) + 2^(b-1);
+ *                dither 0: clip(rint(.), 0, 2^b - 1);  dither 1: the error diffusion above clamped to [0, 2^b - 1], Y over width x height, U and V each over
+ *                their own plane in raster order
+ *   from codes   planes of more than 8 bit first go to 8 bit in a step of their own, as the reference does (:129-130), without dither, clip(rint(.), 0, 255):
+ *                depth_full_range 0: v 2^-(b-8);  1: luma v (255 / (2^b - 1)), chroma ((v - 2^(b-1)) (255 / (2^b - 1))) + 128.  Then on 8-bit codes
+ *                Y = (y - 16) / 219, C = (c - 128) / 224 (full_range 0) or Y = (y - 0) / 255, C = (c - 128) / 255 (1); chroma 1 : 2 where it is subsampled, the
+ *                inverse matrix times 255, dither as above.
+ *   GRAY         planes_to_rgb24 only: R = G = B = clip(rint(((y8 - 16) / 219) 255)): limited -> full whatever full_range says, never dithered (:144-150).
+ * Planes: y [n_frames][height][width], u and v [n_frames][height >> sub_h][width >> sub_w]; uint8 for bits == 8, uint16 (the code in the low bits) for 9..16. */
+typedef struct havc_vformat {
+    int width, height, n_frames;  /* 1..4096 each side; even width with sub_w, even height with sub_h */
+    int family;                   /* 0 YUV, 1 GRAY (planes_to_rgb24 only; u, v and matrix are ignored) */
+    int sub_w, sub_h;             /* log2 chroma subsampling: (1, 1) 4:2:0, (1, 0) 4:2:2, (0, 0) 4:4:4 */
+    int bits;                     /* 8..16; storage uint8 for 8, uint16 above */
+    int matrix;                   /* 1 = 709, 5 = 470bg, 6 = 170m, 9 = 2020ncl */
+    int full_range;               /* range of the matrix step */
+    int depth_full_range;         /* range the > 8 bit -> 8 bit pre-step assumes (planes_to_rgb24 only; 0 in rgb24_to_planes) */
+    int dither;                   /* 0 round half to even, 1 Floyd - Steinberg (0 for GRAY) */
+    int chunk_frames;             /* frames per launch; 0 = the library's choice (havc_yuv420_to_rgb's: 256 MiB of 8-bit 4:2:0 planes) */
+    int reserved;                 /* 0 */
+} havc_vformat;
+/* Every pointer host or device on its own; device operands only enqueue.  Any field outside what is listed, or a NULL pointer: HAVC_E_INVALID, nothing runs. */
+int havc_planes_to_rgb24(havc_ctx* ctx, const void* y, const void* u, const void* v, uint8_t* dst, const havc_vformat* format);
+int havc_rgb24_to_planes(havc_ctx* ctx, const uint8_t* src, void* y, void* u, void* v, const havc_vformat* format);
 /* HAVC_stabilizer(stab=True) (vsdeoldify/__init__.py:2862-2866): vs_chroma_stabilizer_ex (vsslib/vsfilters.py:38-63, 84-157, 216-356) with hue_adjust 'none'
  * and algo 0, then (flicker != 0) vs_reduce_flicker, on a whole clip [n_frames][height][width][3].  VapourSynth, zimg and the ReduceFlicker plugin cannot be
  * executed where the fixtures are made: everything native is an UNPINNED stand-in whose definition is tests/stab_util.py (on top of tests/tweak_util.py), and

@@ -26,6 +26,9 @@ def __getattr__(name):
                 "HAVC_TimeCube", "HAVC_clip_overlay"):
         from . import havc
         return getattr(havc, name)
+    if name in ("VideoClip", "ClipInfo", "DevicePlane", "convert_format_RGB24", "restore_format"):
+        from . import vformat
+        return getattr(vformat, name)
     if name in ("RemasterRender", "RemasterClipRender"):
         from . import remaster_render
         return getattr(remaster_render, name)

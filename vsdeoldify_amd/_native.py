@@ -116,6 +116,12 @@ class ChromaStabParams(C.Structure):
                 ("reserved", C.c_int), ("scene_prev", C.c_void_p), ("scene_next", C.c_void_p)]
 
 
+class VFormat(C.Structure):
+    """`havc_vformat` (include/havc_mi355.h): a clip's size and video format for havc_planes_to_rgb24 / havc_rgb24_to_planes"""
+    _fields_ = [(n, C.c_int) for n in ("width", "height", "n_frames", "family", "sub_w", "sub_h", "bits", "matrix", "full_range", "depth_full_range", "dither",
+                                       "chunk_frames", "reserved")]
+
+
 class AdjustParams(C.Structure):
     """`havc_adjust_params` (include/havc_mi355.h): clip size, normalisation, the affine step and the per-plane gamma tables of havc_adjust_rgb_clip"""
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_frames", C.c_int), ("normalize", C.c_int), ("strength", C.c_double), ("gain", C.c_float * 3),
@@ -227,6 +233,8 @@ SYMBOLS = [
     ("havc_tweak_clip", _I, [_P, _P, _P, _P]),
     ("havc_rgb_to_yuv420", _I, [_P, _P, _P, _P, _P, _I, _I, _I]),
     ("havc_yuv420_to_rgb", _I, [_P, _P, _P, _P, _P, _I, _I, _I]),
+    ("havc_planes_to_rgb24", _I, [_P, _P, _P, _P, _P, _P]),
+    ("havc_rgb24_to_planes", _I, [_P, _P, _P, _P, _P, _P]),
     ("havc_tweak_weights", _I, [_P]),
     ("havc_chroma_stab_clip", _I, [_P, _P, _P, _P]),
     ("havc_chroma_stab_frame_params", _I, [C.c_int64, C.c_int64, C.c_int64, _D, _D, _P]),

@@ -286,6 +286,25 @@ struct TweakRestoreArgs {
 int launch_tweak_back_indexed(const uint8_t* y, const uint8_t* u, const uint8_t* v, uint8_t* dst, const int* yidx, const int* cidx, TweakBackArgs a,
                               hipStream_t s);
 int launch_tweak_forward_restore(const uint8_t* gray, uint8_t* u, uint8_t* v, TweakFwdArgs a, TweakRestoreArgs ra, hipStream_t s);
+// vformat.hip: a clip's own planes (YUV 4:2:0 / 4:2:2 / 4:4:4 or GRAY, 8..16 bit, limited or full range, four matrices) <-> RGB24: the stand-in of
+// tests/vformat_util.py, built on the resampler, the mirroring and the error diffusion above.  The launchers derive every constant from these fields.
+struct VfArgs {
+    int n, h, w;                  // frames of the chunk, frame size (at most TW_MAX_SIDE; even where the chroma is subsampled)
+    int gray, sub_w, sub_h;       // GRAY: one plane; log2 chroma subsampling (1, 1), (1, 0) or (0, 0)
+    int bits;                     // 8: uint8 planes; 9..16: uint16 planes
+    int matrix;                   // 1, 5, 6, 9 (H.273)
+    int full_range;               // range of the matrix step
+    int depth_full_range;         // planes -> RGB24: range of the > 8 bit -> 8 bit step in front of it
+    int dither;                   // 0 round half to even, 1 error diffusion
+    // set by the launchers (vf_constants)
+    float kr, kg, kb, cb_div, cr_div, r_cr, b_cb, g_cr, g_cb;
+    float y_off, y_scale, c_scale;        // planes -> RGB24 on 8-bit codes: Y = (y - y_off) / y_scale, C = (c - 128) / c_scale
+    float depth_mul, depth_half;          // the depth step: limited v 2^-(bits - 8); full v (255 / (2^bits - 1)), chroma (v - 2^(bits - 1)) (..) + 128
+    float ys, yo, cs, co, hi;             // RGB24 -> planes: Y ys + yo, C cs + co, codes clamped to [0, hi]
+    TweakWeights wt;
+};
+int launch_vformat_to_rgb(const void* y, const void* u, const void* v, uint8_t* dst, VfArgs a, hipStream_t s);
+int launch_vformat_from_rgb(const uint8_t* src, void* y, void* u, void* v, VfArgs a, hipStream_t s);
 // chroma_stab.hip: what HAVC_stabilizer(stab=True) adds around those -- the index tables of a chunk, the per-frame sums of the shifted clips,
 // std.AverageFrames on the U / V planes, ReduceFlicker (vsslib/vsfilters.py:38-63, 84-157, 216-356; the stand-ins of tests/stab_util.py)
 struct StabTableArgs {

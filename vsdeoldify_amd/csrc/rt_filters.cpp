@@ -6,6 +6,7 @@
 #include "equalize_ops.h"
 #include "retinex_ops.h"
 #include "tweak_ops.h"
+#include "vformat_ops.h"
 #include "chroma_stab_ops.h"
 #include "lut3d_ops.h"
 #include "overlay_ops.h"
@@ -520,6 +521,86 @@ int havc_yuv420_to_rgb(havc_ctx* c, const uint8_t* y, const uint8_t* u, const ui
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
         a.n = std::min(chunk, n_frames - f0);
         const int e = launch_tweak_back(d_y + (size_t)f0 * pb, d_u + (size_t)f0 * qb, d_v + (size_t)f0 * qb, d_dst + (size_t)f0 * pb * 3, a, c->stream);
+        if (!call.launched(e)) return call.rc;
+    }
+    return call.done();
+}
+
+// ---- convert_format_RGB24 / restore_format: a clip's own planes <-> RGB24 (vformat.hip) ----
+static_assert(sizeof(havc_vformat) == 52, "havc_vformat layout");
+
+static int vformat_check(havc_ctx* c, const char* what, const havc_vformat* f, bool to_rgb, VfArgs& a) {
+    const std::string w(what);
+    if (f->width < 1 || f->height < 1 || f->n_frames <= 0 || f->width > TW_MAX_SIDE || f->height > TW_MAX_SIDE)
+        return fail(c, HAVC_E_INVALID, w + ": bad clip size (at most 4096 x 4096)");
+    if (f->family != 0 && f->family != 1) return fail(c, HAVC_E_INVALID, w + ": family must be 0 (YUV) or 1 (GRAY)");
+    if (f->family == 1 && !to_rgb) return fail(c, HAVC_E_INVALID, w + ": GRAY is not a destination (restore_format sends a GRAY original back as YUV420P8)");
+    const bool sub_ok = f->family == 1 ? (f->sub_w == 0 && f->sub_h == 0) : ((f->sub_w == 1 && (f->sub_h == 0 || f->sub_h == 1)) || (f->sub_w == 0 && f->sub_h == 0));
+    if (!sub_ok) return fail(c, HAVC_E_INVALID, w + ": (sub_w, sub_h) must be (1, 1), (1, 0) or (0, 0), and (0, 0) for GRAY");
+    if ((f->sub_w && (f->width & 1)) || (f->sub_h && (f->height & 1))) return fail(c, HAVC_E_INVALID, w + ": subsampled chroma needs an even width (4:2:x) / height (4:2:0)");
+    if (f->bits < 8 || f->bits > 16) return fail(c, HAVC_E_INVALID, w + ": bits must be 8..16");
+    double kr, kb;
+    if (f->family == 0 && !vf_matrix(f->matrix, kr, kb)) return fail(c, HAVC_E_INVALID, w + ": matrix must be 1 (709), 5 (470bg), 6 (170m) or 9 (2020ncl)");
+    if ((f->full_range | 1) != 1 || (f->depth_full_range | 1) != 1 || (f->dither | 1) != 1)
+        return fail(c, HAVC_E_INVALID, w + ": full_range, depth_full_range and dither must be 0 or 1");
+    if (!to_rgb && f->depth_full_range) return fail(c, HAVC_E_INVALID, w + ": depth_full_range belongs to planes_to_rgb24 and must be 0 here");
+    if (f->family == 1 && f->dither) return fail(c, HAVC_E_INVALID, w + ": GRAY -> RGB24 is not dithered (the reference asks for none)");
+    if (f->chunk_frames < 0 || f->reserved != 0) return fail(c, HAVC_E_INVALID, w + ": chunk_frames must be >= 0 and reserved 0");
+    a = VfArgs{};
+    a.h = f->height; a.w = f->width; a.gray = f->family; a.sub_w = f->sub_w; a.sub_h = f->sub_h; a.bits = f->bits; a.matrix = f->family ? 1 : f->matrix;
+    a.full_range = f->full_range; a.depth_full_range = f->depth_full_range; a.dither = f->dither;
+    return HAVC_OK;
+}
+
+// Frames per launch: havc_yuv420_to_rgb's rule (tweak_chunk_frames), so the same clip goes through in the same number of launches.  The diffusing kernels
+// are one block per frame (and plane): every launch pays a whole frame's latency, and a clip split in two takes twice as long.
+static int vformat_chunk_frames(const havc_vformat* f) { return tweak_chunk_frames(f->width, f->height, f->n_frames, f->chunk_frames); }
+
+int havc_planes_to_rgb24(havc_ctx* c, const void* y, const void* u, const void* v, uint8_t* dst, const havc_vformat* f) {
+    if (!c || !y || !dst || !f || (f->family == 0 && (!u || !v))) return fail(c, HAVC_E_INVALID, "planes_to_rgb24: bad args");
+    VfArgs a;
+    int rc = vformat_check(c, "planes_to_rgb24", f, true, a);
+    if (rc) return rc;
+    Call call(c, "planes_to_rgb24");
+    const bool yuv = f->family == 0;
+    const size_t bps = f->bits > 8 ? 2 : 1, n = (size_t)f->n_frames, npix = (size_t)f->width * f->height;
+    const size_t pb = npix * bps, qb = yuv ? (size_t)(f->width >> f->sub_w) * (f->height >> f->sub_h) * bps : 0;
+    Call::Pack planes(SCR_TWEAK_YUV);                                    // the host planes among y, u, v
+    call.add(planes, y, n * pb);
+    if (yuv) { call.add(planes, u, n * qb); call.add(planes, v, n * qb); }
+    call.reserve(planes);
+    const uint8_t* d_y = call.in(planes, (const uint8_t*)y, n * pb);
+    const uint8_t *d_u = yuv ? call.in(planes, (const uint8_t*)u, n * qb) : nullptr, *d_v = yuv ? call.in(planes, (const uint8_t*)v, n * qb) : nullptr;
+    uint8_t* d_dst = call.out(SCR_OUT, dst, n * npix * 3);
+    if (call.rc) return call.rc;
+    const int chunk = vformat_chunk_frames(f);
+    for (int f0 = 0; f0 < f->n_frames; f0 += chunk) {
+        a.n = std::min(chunk, f->n_frames - f0);
+        const int e = launch_vformat_to_rgb(d_y + (size_t)f0 * pb, yuv ? d_u + (size_t)f0 * qb : nullptr, yuv ? d_v + (size_t)f0 * qb : nullptr,
+                                            d_dst + (size_t)f0 * npix * 3, a, c->stream);
+        if (!call.launched(e)) return call.rc;
+    }
+    return call.done();
+}
+
+int havc_rgb24_to_planes(havc_ctx* c, const uint8_t* src, void* y, void* u, void* v, const havc_vformat* f) {
+    if (!c || !src || !y || !u || !v || !f) return fail(c, HAVC_E_INVALID, "rgb24_to_planes: bad args");
+    VfArgs a;
+    int rc = vformat_check(c, "rgb24_to_planes", f, false, a);
+    if (rc) return rc;
+    Call call(c, "rgb24_to_planes");
+    const size_t bps = f->bits > 8 ? 2 : 1, n = (size_t)f->n_frames, npix = (size_t)f->width * f->height;
+    const size_t pb = npix * bps, qb = (size_t)(f->width >> f->sub_w) * (f->height >> f->sub_h) * bps;
+    const uint8_t* d_src = call.in(SCR_IN, src, n * npix * 3);
+    Call::Pack planes(SCR_TWEAK_YUV);                                    // the host planes among y, u, v
+    call.add(planes, y, n * pb); call.add(planes, u, n * qb); call.add(planes, v, n * qb);
+    call.reserve(planes);
+    uint8_t *d_y = call.out(planes, (uint8_t*)y, n * pb), *d_u = call.out(planes, (uint8_t*)u, n * qb), *d_v = call.out(planes, (uint8_t*)v, n * qb);
+    if (call.rc) return call.rc;
+    const int chunk = vformat_chunk_frames(f);
+    for (int f0 = 0; f0 < f->n_frames; f0 += chunk) {
+        a.n = std::min(chunk, f->n_frames - f0);
+        const int e = launch_vformat_from_rgb(d_src + (size_t)f0 * npix * 3, d_y + (size_t)f0 * pb, d_u + (size_t)f0 * qb, d_v + (size_t)f0 * qb, a, c->stream);
         if (!call.launched(e)) return call.rc;
     }
     return call.done();
