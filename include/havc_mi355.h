@@ -778,6 +778,28 @@ typedef struct havc_overlay_params {
 } havc_overlay_params;
 /* base, overlay, mask, dst: host or device pointers, each on its own; dst is none of the inputs.  Device operands: the call only enqueues.  One launch. */
 int havc_overlay_clip(havc_ctx* ctx, const uint8_t* base, const uint8_t* overlay, const uint8_t* mask, uint8_t* dst, const havc_overlay_params* params);
+/* The project's yardstick on the device: per-pixel CIEDE2000 (Sharma, Wu, Dalal 2005) between two RGB24 clips a, b [n_frames][height][width][3], in float64,
+ * as oracle/imaging.py delta_e00_images defines it (the parity metric of BASELINE.json): sRGB -> linear through a 256-entry float64 table, the XYZ matrix and
+ * white point written there, f(t) = t > 0.008856 ? cbrt(t) : 7.787 t + 16 / 116, and the oracle's branches on C1' C2' == 0 and on hue differences beyond
+ * +-180 degrees exactly as written.  Identical pixels give exactly 0.0.  One record per frame: */
+#define HAVC_DE_BINS 1025             /* bin i counts floor(dE * 64) == i; the last bin collects everything at or above 16.0 */
+typedef struct havc_de_rec {
+    double sum;                       /* sum of dE over the frame: per-block sums in a fixed lane order, the blocks added in index order -- the same bits every run */
+    double max;                       /* largest dE of the frame (0.0 when all pixels are equal) */
+    uint64_t sse[3];                  /* per channel: exact sum of squared byte differences (PSNR is derived from it on the host) */
+    uint32_t hist[HAVC_DE_BINS];
+    uint32_t reserved;                /* 0 */
+} havc_de_rec;                        /* 4144 bytes */
+/* a, b: host or device pointers, each on its own.  recs: n_frames records, host or device.  map: NULL, or [n_frames][height][width] float64, host or device:
+ * every pixel's dE.  With device operands only, the call only enqueues.  One pass over the pixels and one small launch for the sums per chunk of frames; a
+ * chunk is as many frames as keep the per-block partial sums inside their scratch slot (64 MiB; HAVC_DE_SCRATCH_BYTES, read when the context is created,
+ * lowers that so tests reach a second chunk at small sizes) and a staged host map under 256 MiB.  A NULL pointer, a non-positive size or a frame of more
+ * than 2^30 pixels: HAVC_E_INVALID, nothing runs. */
+int havc_delta_e_clip(havc_ctx* ctx, const uint8_t* a, const uint8_t* b, int width, int height, int n_frames, havc_de_rec* recs, double* map);
+/* The sRGB -> linear table the kernel reads: 256 float64, host memory, uploaded once and kept with the context.  vsdeoldify_amd/metrics.py hands in the
+ * oracle's own numpy expression, which makes the table equal to the oracle's bit for bit.  A context that was never given one builds it with the C library's
+ * pow on first use (the same formula; the last bit of an entry may differ from numpy's). */
+int havc_delta_e_set_table(havc_ctx* ctx, const double* srgb_to_linear256);
 /* the per-pixel half of luma_adjusted_levels (vsslib/imfilters.py:335-372): cv2 RGB->YUV, Y' = lut[Y], YUV->RGB.  The caller
  * derives the 256-entry table from havc_image_luma exactly like the reference (vsdeoldify_amd/imfilters.py). */
 int havc_luma_lut(havc_ctx* ctx, const uint8_t* img, const uint8_t* lut256, uint8_t* out, int width, int height);

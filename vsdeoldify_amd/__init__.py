@@ -29,6 +29,9 @@ def __getattr__(name):
     if name in ("VideoClip", "ClipInfo", "DevicePlane", "convert_format_RGB24", "restore_format"):
         from . import vformat
         return getattr(vformat, name)
+    if name in ("clip_delta_e", "DeltaEReport"):
+        from . import metrics
+        return getattr(metrics, name)
     if name in ("RemasterRender", "RemasterClipRender"):
         from . import remaster_render
         return getattr(remaster_render, name)

@@ -152,6 +152,10 @@ SCENE_REC_DTYPE = np.dtype([("sum_y", "<i8"), ("sad", "<i8"), ("sum_raw", "<i8")
 # numpy mirror of `havc_edge_rec`: one record per frame
 EDGE_REC_DTYPE = np.dtype([("sum_y", "<i8"), ("sad_prev", "<i8"), ("sad_next", "<i8"), ("sum_masked", "<i8")], align=True)
 
+# numpy mirror of `havc_de_rec`: one record per frame (havc_delta_e_clip)
+DE_BINS = 1025
+DE_REC_DTYPE = np.dtype([("sum", "<f8"), ("max", "<f8"), ("sse", "<u8", (3,)), ("hist", "<u4", (DE_BINS,)), ("reserved", "<u4")], align=True)
+
 
 class NativeLibraryError(RuntimeError):
     pass
@@ -243,6 +247,8 @@ SYMBOLS = [
     ("havc_adjust_frame_params", _I, [_P, C.c_int64, _P]),
     ("havc_lut3d_clip", _I, [_P, _P, _P, _P, _P, _P, _P]),
     ("havc_overlay_clip", _I, [_P, _P, _P, _P, _P, _P]),
+    ("havc_delta_e_clip", _I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    ("havc_delta_e_set_table", _I, [_P, _P]),
     ("havc_luma_lut", _I, [_P, _P, _P, _P, _I, _I]),
     ("havc_restore_color_gradient", _I, [_P, _P, _P, _P, _I, _I, _D, _I, _D, _D, _I, _I]),
     ("havc_recover_color_clip", _I, [_P, _P, _P, _P, _P]),

@@ -346,6 +346,15 @@ struct OverlayArgs {
     float opacity;
 };
 int launch_overlay(const uint8_t* base, const uint8_t* ov, const uint8_t* mask, uint8_t* dst, OverlayArgs a, hipStream_t s);
+// metrics.hip: per-pixel CIEDE2000 between two RGB24 clips in float64 (metrics_ops.h has the arithmetic, the restatement of oracle/imaging.py).  DeRec is the
+// device image of havc_de_rec (include/havc_mi355.h); `max` travels as the bit pattern of a non-negative double, which orders like the value.
+#define DE_BINS 1025
+#define DE_BLOCK_PIXELS 1024          // 256 threads x 4 pixels: one partial sum per block
+struct DeRec { double sum; unsigned long long max_bits; unsigned long long sse[3]; unsigned hist[DE_BINS]; unsigned reserved; };
+inline int64_t delta_e_blocks(int64_t npix) { return (npix + DE_BLOCK_PIXELS - 1) / DE_BLOCK_PIXELS; }       // per frame
+// a, b: [n][npix][3]; lin: the 256-entry sRGB -> linear table; rec: n zero-filled records; partials: n * delta_e_blocks(npix) doubles; map: NULL or [n][npix].
+// n <= 65535 (grid y), npix <= 2^30.  Two launches: the pixels, then the per-frame sums in block order.
+int launch_delta_e(const uint8_t* a, const uint8_t* b, const double* lin, DeRec* rec, double* partials, double* map, int n, int64_t npix, hipStream_t s);
 // separable polyphase resample of interleaved u8 RGB (tap tables from the host; Spline64 = harness stand-in
 // for zimg resize.Spline64).  orig != null fuses chroma_post_process (luma of orig, chroma of the resampled).
 int launch_resize_passes(const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh, int n_frames, float* tmp,
@@ -401,6 +410,7 @@ void preload_tweak_clip();
 void preload_chroma_stab();
 void preload_lut3d();
 void preload_overlay();
+void preload_metrics();
 void preload_ddcolor();
 void preload_colormnet();
 void preload_colormnet_net();

@@ -88,7 +88,7 @@ static void preload_device_locked(int dev) {
     static uint64_t done = 0;                              // guarded by g_setup_mu
     if (done & (1ull << (dev & 63))) return;
     preload_conv_pipe(); preload_conv_igemm(); preload_elementwise(); preload_zhang(); preload_attention(); preload_colorfilters();
-    preload_tweaks(); preload_stabilizer(); preload_tiles(); preload_scdetect(); preload_scfilter(); preload_scedge(); preload_equalize(); preload_retinex(); preload_tweak_clip(); preload_chroma_stab(); preload_lut3d(); preload_overlay(); preload_recover(); preload_ddcolor(); preload_colormnet(); preload_colormnet_net(); preload_precise(); preload_precise2(); preload_remaster();
+    preload_tweaks(); preload_stabilizer(); preload_tiles(); preload_scdetect(); preload_scfilter(); preload_scedge(); preload_equalize(); preload_retinex(); preload_tweak_clip(); preload_chroma_stab(); preload_lut3d(); preload_overlay(); preload_metrics(); preload_recover(); preload_ddcolor(); preload_colormnet(); preload_colormnet_net(); preload_precise(); preload_precise2(); preload_remaster();
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(scratch_warm_kernel));
     (void)hipGetLastError();
@@ -114,6 +114,10 @@ int havc_create(havc_ctx** out, int device_id) {
     if (const char* e = getenv("HAVC_DESC_LIMIT_BYTES")) {
         const unsigned long long v = strtoull(e, nullptr, 0);
         if (v >= 4096 && v <= 0xE0000000ull) c->desc_limit = v;
+    }
+    if (const char* e = getenv("HAVC_DE_SCRATCH_BYTES")) {
+        const unsigned long long v = strtoull(e, nullptr, 0);
+        if (v >= 8 && v <= (64ull << 20)) c->de_partials_limit = v;
     }
     if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess ||
@@ -158,6 +162,7 @@ static void havc_destroy_unlocked(havc_ctx* c) {
     }
     for (int i = 0; i < SCR_COUNT; ++i)
         if (c->scratch[i]) (void)hipFree(c->scratch[i]);
+    if (c->de_table) (void)hipFree(c->de_table);
     for (auto& kv : c->resize_tables) { (void)hipFree(kv.second.d_start); (void)hipFree(kv.second.d_w); }
     for (auto& p : c->tag_events) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     (void)hipEventDestroy(c->ev0);

@@ -10,6 +10,8 @@
 #include "chroma_stab_ops.h"
 #include "lut3d_ops.h"
 #include "overlay_ops.h"
+#include "metrics_ops.h"
+#include <cstddef>
 
 extern "C" {
 
@@ -907,6 +909,66 @@ int havc_overlay_clip(havc_ctx* c, const uint8_t* base, const uint8_t* overlay, 
     uint8_t* d_dst = call.out(SCR_OUT, dst, bb);
     if (call.rc) return call.rc;
     call.launched(launch_overlay(d_base, d_ov, d_mask, d_dst, a, c->stream));
+    return call.done();
+}
+
+// ---- per-pixel CIEDE2000 between two clips (metrics.hip) ----
+static_assert(sizeof(DeRec) == sizeof(havc_de_rec) && sizeof(havc_de_rec) == 4144 && HAVC_DE_BINS == DE_BINS && DE_BINS == DE_HIST_BINS, "havc_de_rec layout");
+static_assert(offsetof(DeRec, max_bits) == offsetof(havc_de_rec, max) && offsetof(DeRec, sse) == offsetof(havc_de_rec, sse) &&
+              offsetof(DeRec, hist) == offsetof(havc_de_rec, hist), "havc_de_rec layout");
+
+// the context's sRGB -> linear table: its own 2 KiB, allocated once; the copy has left the caller's memory when this returns
+static void de_table_upload(Call& call, const double* host256) {
+    havc_ctx* c = call.c;
+    if (call.rc) return;
+    if (!c->de_table) {
+        SetupLock setup;
+        if (!call.check(hipMalloc((void**)&c->de_table, 256 * sizeof(double)), "hipMalloc")) { c->de_table = nullptr; return; }
+        c->stats.bytes_resident += 256 * sizeof(double);
+    }
+    call.copy(c->de_table, host256, 256 * sizeof(double), hipMemcpyHostToDevice);
+    call.sync();
+}
+
+int havc_delta_e_set_table(havc_ctx* c, const double* srgb_to_linear256) {
+    if (!c || !srgb_to_linear256) return fail(c, HAVC_E_INVALID, "delta_e_set_table: bad args");
+    if (is_device_ptr(srgb_to_linear256)) return fail(c, HAVC_E_INVALID, "delta_e_set_table: the table is host memory");
+    Call call(c, "delta_e_set_table");
+    de_table_upload(call, srgb_to_linear256);
+    return call.done();
+}
+
+int havc_delta_e_clip(havc_ctx* c, const uint8_t* a, const uint8_t* b, int width, int height, int n_frames, havc_de_rec* recs, double* map) {
+    if (!c || !a || !b || !recs) return fail(c, HAVC_E_INVALID, "delta_e_clip: bad args");
+    if (n_frames <= 0 || width <= 0 || height <= 0 || (int64_t)width * height > ((int64_t)1 << 30))
+        return fail(c, HAVC_E_INVALID, "delta_e_clip: bad clip size (at most 2^30 pixels per frame)");
+    Call call(c, "delta_e_clip");
+    if (!c->de_table) {
+        double lin[256];
+        for (int v = 0; v < 256; ++v) lin[v] = de_srgb_linear(v);
+        de_table_upload(call, lin);
+    }
+    const int64_t npix = (int64_t)width * height, nb = delta_e_blocks(npix);
+    const size_t cb = (size_t)n_frames * npix * 3, rb = (size_t)n_frames * sizeof(DeRec), mb = (size_t)npix * sizeof(double);
+    const bool host_map = map && !is_device_ptr(map);
+    // frames per chunk: a launch takes at most 65535 (grid y), the partial sums stay inside their slot, a host map is staged in pieces under 256 MiB
+    int64_t chunk = std::min<int64_t>(n_frames, 65535);
+    chunk = std::min<int64_t>(chunk, (int64_t)(c->de_partials_limit / sizeof(double)) / nb);
+    if (host_map) chunk = std::min<int64_t>(chunk, (int64_t)(((size_t)256 << 20) / mb));
+    chunk = std::max<int64_t>(chunk, 1);
+    const uint8_t* d_a = call.in(SCR_IN, a, cb);
+    const uint8_t* d_b = call.in(SCR_IN2, b, cb);
+    DeRec* d_rec = (DeRec*)call.out(SCR_SMALL, recs, rb);
+    double* d_part = (double*)call.scratch(SCR_DE_PARTIALS, (size_t)chunk * nb * sizeof(double));
+    double* d_map = host_map ? (double*)call.scratch(SCR_OUT, (size_t)chunk * mb) : map;
+    if (call.rc) return call.rc;
+    call.zero(d_rec, rb);
+    for (int64_t f0 = 0; f0 < n_frames; f0 += chunk) {
+        const int n = (int)std::min<int64_t>(chunk, n_frames - f0);
+        double* m = !map ? nullptr : (host_map ? d_map : d_map + f0 * npix);
+        if (!call.launched(launch_delta_e(d_a + f0 * npix * 3, d_b + f0 * npix * 3, c->de_table, d_rec + f0, d_part, m, n, npix, c->stream), 2)) break;
+        if (host_map) call.copy(map + f0 * npix, d_map, (size_t)n * mb, hipMemcpyDeviceToHost);             // the next chunk reuses the slot
+    }
     return call.done();
 }
 

@@ -90,6 +90,7 @@ enum ScratchSlot {
                                             //   their own (havc_rgb_to_yuv420 / havc_yuv420_to_rgb): host planes on their way in or out
     SCR_CHROMA_STAB = SCR_RESIZE_ROWS,      //   havc_chroma_stab_clip: the workspace of a CHUNK of frames -- planes, the shifted clips, tables, sums (bounded by the chunk)
     SCR_LUT3D = SCR_RESIZE_ROWS,            //   havc_lut3d_clip: the table as 16-byte points, and in front of them a host table on its way in
+    SCR_DE_PARTIALS = SCR_RESIZE_ROWS,      //   havc_delta_e_clip: the per-block partial sums [frame][block] of a CHUNK of frames (bounded by de_partials_limit)
     // 8-11: the pipelined host clip (havc_colorize_clip_host), double-buffered by batch parity; the ONE-SHOT ColorMNet reads reuse them
     SCR_CLIP_SRC = 8,                  // 8, 9: source batches, SCR_CLIP_SRC + (batch & 1)
     SCR_SIM = SCR_CLIP_SRC,            //   one-shot read: similarity map [B][N][HW]; havc_local_attention: the attention map
@@ -124,6 +125,8 @@ struct havc_ctx {
     bool two_streams = true;              // HAVC_TWO_STREAMS=0 serialises the two generators (A/B measurements)
     bool range_check = false;             // HAVC_RANGE_CHECK / havc_range_check_enable: scan every op's destination for inf / NaN / abs-max
     uint64_t nt_store_bytes = 0;          // conv outputs at least this large are written with non-temporal stores (0 = never); HAVC_NT_STORE_MB
+    double* de_table = nullptr;           // havc_delta_e_clip: the sRGB -> linear table (256 float64), its own allocation: it outlives every call
+    uint64_t de_partials_limit = 64ull << 20;   // bytes of partial sums one chunk of havc_delta_e_clip may take; HAVC_DE_SCRATCH_BYTES lowers it (tests)
     uint64_t desc_limit = 0xE0000000ull;  // bytes one conv launch may address per operand (32-bit buffer descriptors);
                                           // HAVC_DESC_LIMIT_BYTES lowers it so tests reach the frame-chunking path at small sizes
     std::mutex mu;
